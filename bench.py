@@ -6,12 +6,17 @@ over every atmosphere column resident on the GPU.  Workload (config.workload):
   c3 (default)  1000 FALC-perturbed CaII columns per GPU, ray-dependent line profiles
                 (BASELINE.json configs[2]; weak scaling: columns per GPU fixed)
   c2            the single FALC CaII column (configs[1]; 45 wavefronts -- latency bound by
-                construction, reported inside every run as `falc_single_column`)
+                construction, reported inside every --full run as `falc_single_column`)
   c4            FALC-perturbed Ca+H columns (configs[3] per-GPU share, 1250 columns); its one-GPU share is
-                also measured inside every default run (`c4_share`)
+                also measured inside every --full run of c3 (`c4_share`)
   c5            the CaII temperature response function (configs[4]): 164 perturbed columns, sharded over the ranks
 value = depth-points x wavelengths x rays updated per second, whole job.
 Inputs are resident in HBM before the timed region.  One JSON line on stdout (rank 0).
+
+A plain run sets up, warms up, times --steps steps and prints the line.  --full adds everything else the line can carry:
+the roofline block (kernel timings of their own), the CPU baseline, the single-column section, the C4 share and the
+comparisons with the reference's vectors.  --dump-outputs DIR writes what the last timed step computed (rank 0's columns)
+as DIR/<name>.npy in float64, at most 64 MB (a fixed, seeded sample of the columns where the whole would be larger).
 """
 import argparse
 import json
@@ -73,6 +78,39 @@ def stats_ms(times):
     t = np.asarray(times) * 1e3
     return dict(min=float(t.min()), median=float(np.median(t)), max=float(t.max()), p10=float(np.percentile(t, 10)),
                 p90=float(np.percentile(t, 90)), n=int(t.size))
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6       # all files of --dump-outputs together, .npy headers included
+NPY_HEADER_BYTES = 128
+
+
+def write_outputs(outdir, arrays):
+    """--dump-outputs: every array as outdir/<name>.npy in float64"""
+    os.makedirs(outdir, exist_ok=True)
+    total = sum(8 * np.asarray(a).size + NPY_HEADER_BYTES for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, 'outputs of %d bytes exceed the dump limit' % total
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + '.npy'), np.asarray(a, dtype=np.float64))
+
+
+def engine_outputs(eng, dJ, dP, seed=0):
+    """what a caller of the timed loop receives after its last step: the monitors (dJ, dPops) and, per column, J, I, the
+    populations n and the per-column monitors.  Where all columns would pass DUMP_LIMIT_BYTES, a fixed sample of them drawn
+    with `seed` (sorted; its indices in `columns`)"""
+    from lightspinner_amd import _capi
+    what = dict(J=_capi.LSX_J, I=_capi.LSX_I, n=_capi.LSX_N, dJ_col=_capi.LSX_DJ_COL, dPops_col=_capi.LSX_DPOPS_COL)
+    per_col = sum(8 * int(np.prod(eng._shape(w), dtype=np.int64)) for w in what.values())
+    ncol = eng.ncol
+    keep = int(min(ncol, (DUMP_LIMIT_BYTES - 8 * (ncol + 2) - NPY_HEADER_BYTES * (len(what) + 2)) // per_col))
+    if keep >= ncol:
+        cols = np.arange(ncol)
+        out = {name: eng.get(w) for name, w in what.items()}
+    else:
+        cols = np.sort(np.random.default_rng(seed).choice(ncol, keep, replace=False))
+        out = {name: np.concatenate([eng.get(w, int(c), 1) for c in cols]) for name, w in what.items()}
+    out['columns'] = cols
+    out['monitors'] = np.array([dJ, np.nan if dP is None else dP])
+    return out
 
 
 def dist_env():
@@ -146,11 +184,15 @@ def run_c5(args, rank, local_rank, world):
         dist.all_gather_object(every, dict(rank=rank, seconds=dt_own, world_seen=dist.get_world_size(), backend=dist.get_backend(),
                                            shard=[int(x) for x in out['shard']]))
         scaling_record = dict(world_seen=dist.get_world_size(), backend=dist.get_backend(), per_rank=every, seconds_max_over_ranks=dt)
-    ref = dict(np.load(os.path.join(gold, 'rf_ca.npz')))
-    err = 0.0
-    for k in [int(k) for k in ref['ks']]:
-        r = (ref['k%dp_I' % k][:, -1] - ref['k%dm_I' % k][:, -1]) / ref['base_I'][:, -1]
-        err = max(err, float(np.max(np.abs(out['rf'][:, k] - r)) / np.max(np.abs(r))))
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, dict(rf=out['rf'], I=out['I'], I_base=out['I_base'], n_base=out['n_base']))
+    ref = dict(np.load(os.path.join(gold, 'rf_ca.npz'))) if args.full else None
+    err = None
+    if ref is not None:
+        err = 0.0
+        for k in [int(k) for k in ref['ks']]:
+            r = (ref['k%dp_I' % k][:, -1] - ref['k%dm_I' % k][:, -1]) / ref['base_I'][:, -1]
+            err = max(err, float(np.max(np.abs(out['rf'][:, k] - r)) / np.max(np.abs(r))))
     col_iters = int(out['n_iter'].sum()) + out['n_iter_base'] * world     # every rank solves the base column itself
     units = prob.work_units_per_column() * col_iters
     steps = int(out['n_iter'].max()) + out['n_iter_base']
@@ -161,7 +203,7 @@ def run_c5(args, rank, local_rank, world):
         return
     result = dict(
         metric='depth_points_x_wavelengths_x_rays_per_sec', value=units / dt, unit='point-updates/s', n_gpus=world, steps=steps,
-        warmup=0, ms_per_step=dt / steps * 1e3, higher_is_better=True, scaling='strong', vs_baseline=None, dtype='f64',
+        warmup=0, ms_per_step=dt / steps * 1e3, higher_is_better=True, scaling='strong', vs_baseline=None, dtype='f64', full=args.full,
         data='FALC CaII + reference-generated temperature perturbations (tests/golden/rf_ca_inputs.npz)',
         config=dict(workload='C5: CaII temperature response function, %d perturbed columns (T[k] +- 25 K at %d depths) + base, '
                              'per-column convergence' % (2 * len(ks), len(ks)), columns_total=2 * len(ks) + 1,
@@ -170,7 +212,7 @@ def run_c5(args, rank, local_rank, world):
                                perturbed_iterations_min=int(out['n_iter'].min()), perturbed_iterations_max=int(out['n_iter'].max()),
                                column_iterations=col_iters, rf_shape=list(out['rf'].shape),
                                max_abs_err_vs_reference_rf_over_max=err,
-                               reference_depths_checked=[int(k) for k in ref['ks']],
+                               reference_depths_checked=[int(k) for k in ref['ks']] if ref is not None else None,
                                note='the reference runs these 165 MALI solves one after the other in pure Python (~2 h here)'),
         roofline=None, cpu_baseline=None)
     if scaling_record is not None:
@@ -478,6 +520,11 @@ def main():
     ap.add_argument('--dry-run', action='store_true',
                     help='launcher check without a GPU: the ranks rendezvous over gloo, all-reduce(MAX) their rank and rank 0 '
                          'prints a JSON line with value null')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the timed steps: roofline block, CPU baseline, single-column section, C4 share, '
+                         'comparisons with the reference')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed (rank 0) as DIR/<name>.npy, float64, at most 64 MB')
     args = ap.parse_args()
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
@@ -504,7 +551,7 @@ def main():
     t_gen = time.time() - t0
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:      # CPU baseline: rank 0 at N = 1 only
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:      # CPU baseline: rank 0 at N = 1 only
         cpu = cpu_baseline(prob, batch, prof)
 
     # ---- GPU ---------------------------------------------------------------------------
@@ -543,6 +590,8 @@ def main():
         torch.cuda.synchronize()
 
     dt, per_step, dJ, dP = timed_steps(eng, reducer, args.steps, args.warmup, barrier)
+    if args.dump_outputs and rank == 0:         # before anything else runs on the engine (the roofline block calls it again)
+        write_outputs(args.dump_outputs, engine_outputs(eng, dJ, dP))
     # the scaling record proves itself (round 5): what every rank saw -- its own time for the K steps, the world size and backend of
     # the process group it was in, the sweep mapping its engine ran and its options signature -- gathered onto rank 0's line
     scaling_record = None
@@ -562,11 +611,11 @@ def main():
     units = prob.work_units_per_column() * ncol * world * args.steps
     result = None
     if rank == 0:
-        roofline = roofline_block(eng, lib, prob, ncol, args.workload, args.kernel_reps)
+        roofline = roofline_block(eng, lib, prob, ncol, args.workload, args.kernel_reps) if args.full else None
 
         # ---- parity + single-column (C2) numbers in the same run -----------------------
         single = None
-        if not args.no_single_column:
+        if args.full and not args.no_single_column:
             p1, b1, r1 = fixtures.load_problem_npz(os.path.join(ROOT, 'tests', 'golden', 'falc_ca.npz'))
             e1 = Engine(p1, 1, device=local_rank, stream=ts.cuda_stream, lib=lib)
             t_runs = []
@@ -616,7 +665,7 @@ def main():
 
         result = dict(metric='depth_points_x_wavelengths_x_rays_per_sec', value=units / dt, unit='point-updates/s',
                       n_gpus=world, steps=args.steps, warmup=args.warmup, ms_per_step=dt / args.steps * 1e3,
-                      higher_is_better=True, scaling='weak', vs_baseline=None, dtype='f64', data='synthetic',
+                      higher_is_better=True, scaling='weak', vs_baseline=None, dtype='f64', data='synthetic', full=args.full,
                       config=dict(workload={'c2': 'C2: single FALC 82-depth CaII column, 5 rays',
                                             'c3': 'C3: %d FALC-perturbed CaII columns per GPU, 82 depth x 287 wavelengths x 5 rays x 2 directions' % ncol,
                                             'c4': 'C4 share: %d FALC-perturbed Ca+H columns per GPU, 82 depth x 777 wavelengths x 5 rays x 2' % ncol,
@@ -647,9 +696,9 @@ def main():
             result.update(rehearsal)
     eng.close()
     del batch
-    if rank == 0 and world == 1 and args.workload == 'c3' and not args.no_c4_share:
+    if args.full and rank == 0 and world == 1 and args.workload == 'c3' and not args.no_c4_share:
         result['c4_share'] = measure_share('c4', 1250, local_rank, lib, torch)
-    if rank == 0:
+    if args.full and rank == 0:
         # short keys LAST, so that they survive a reader that keeps only the tail of the line: the headline workload and, at N = 1,
         # the north-star workload's per-GPU share (BASELINE.json: 10^4 Ca+H columns over 8 GPUs), each with its roofline fractions
         r = result['roofline']

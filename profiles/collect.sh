@@ -7,7 +7,7 @@
 # pass that fails or times out is reported and STOPS the collection (no further GPU step after a killed one).
 TAG=$1; shift
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-ARGS="--steps 5 --warmup 1 --no-cpu-baseline --no-single-column --no-c4-share --kernel-reps 5 $*"
+ARGS="--full --steps 5 --warmup 1 --no-cpu-baseline --no-single-column --no-c4-share --kernel-reps 5 $*"
 rc=0
 run_pass() {   # name, rocprofv3 options...
   local name=$1; shift

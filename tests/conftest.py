@@ -19,7 +19,7 @@ def pytest_configure(config):
 # that test runs this process has.  The test only collects their output.
 REHEARSALS = {
     'c3-columns': ['--columns', '200', '--steps', '5', '--warmup', '2', '--no-cpu-baseline', '--no-single-column'],
-    'c5-response-function': ['--workload', 'c5'],
+    'c5-response-function': ['--workload', 'c5', '--full'],      # --full: the comparison with the reference's rf
 }
 _rehearsal_procs = {}
 

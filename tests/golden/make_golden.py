@@ -12,7 +12,7 @@ under /root/reference is touched:
     arrays (numpy<1.25 semantics; only used for list membership in setup).
 (np.bool, used at rh_method.py:124, exists again in numpy 2.x.)
 
-Usage:  python tests/golden/make_golden.py [units] [falc_ca] [falc_cah] [falc_ca_vlos] [falc_c] [falc_fe] [falc_mg] [falc_all] [rf] [rf_inputs] [setup] [all]
+Usage:  python tests/golden/make_golden.py [units] [falc_ca] [falc_cah] [falc_ca_vlos] [falc_c] [falc_fe] [falc_mg] [falc_all] [rf] [rf_inputs] [setup] [live_ref] [all]
 """
 import os
 import sys
@@ -531,6 +531,55 @@ def gen_setup():
     save('setup_falc.npz', d)
 
 
+def gen_live_ref(n_iter=6):
+    """What tests/test_reference_live.py compares with: the reference's FALC CaII Context (test.py's set-up) through six MALI
+    iterations, and the merged wavelength grid of RadiativeSet([CaII, H_6]) with Ca and H active.  Everything falc_ca.npz and
+    setup_falc.npz already hold (vBroad, per transition Nblue / active / aDamp / phi / wphi, iterations 1-5, C, the grid, its
+    blueIdx, the transitions' grids and alpha, the active sets) is checked here to be bit for bit what this run computes; the
+    file keeps only the rest: each line's wlambda, iteration 6 (dJ, J, I) and its statistical equilibrium (dPops, n)."""
+    ca = dict(np.load(os.path.join(HERE, 'falc_ca.npz')))
+    st = dict(np.load(os.path.join(HERE, 'setup_falc.npz')))
+    d = {}
+    ctx = build_ctx(['Ca'])
+    atom = ctx.activeAtoms[0]
+    assert np.array_equal(atom.vBroad, ca['a0_vBroad'])
+    for kr, t in enumerate(atom.trans):
+        assert t.Nblue == ca['t_Nblue'][kr] and np.array_equal(t.active, ca['t_active'][kr])
+        if t.isLine:
+            aDamp = t.transModel.damping(ctx.atmos, atom.vBroad, atom.hPops.n[0])[0]
+            phi = ca['t%d_phi' % kr]
+            assert np.array_equal(aDamp, ca['t%d_aDamp' % kr]) and np.array_equal(t.wphi, ca['t%d_wphi' % kr])
+            assert np.array_equal(t.phi, phi if phi.ndim == 4 else np.broadcast_to(phi[:, None, None, :], t.phi.shape))
+            d['t%d_wlambda' % kr] = np.array(t.wlambda())
+    for it in range(1, n_iter + 1):
+        dJ = ctx.formal_sol_gamma_matrices()
+        assert np.array_equal(atom.C, ca['a0_C'])
+        if it < n_iter:
+            assert dJ == ca['fs%d_dJ' % it] and np.array_equal(ctx.J, ca['fs%d_J' % it]) and np.array_equal(ctx.I, ca['fs%d_I' % it])
+        else:
+            d['fs%d_dJ' % it], d['fs%d_J' % it], d['fs%d_I' % it] = np.float64(dJ), ctx.J.copy(), ctx.I.copy()
+        if it > 3:
+            dPops = ctx.stat_equil()
+            if it < n_iter:
+                assert dPops == ca['se%d_dPops' % it] and np.array_equal(ctx.eqPops['Ca'].n, ca['se%d_n_a0' % it])
+            else:
+                d['se%d_dPops' % it], d['se%d_n' % it] = np.float64(dPops), np.array(ctx.eqPops['Ca'].n)
+    aSet = RadiativeSet([CaII_atom(), H_6_atom()])
+    aSet.set_active('Ca', 'H')
+    spect = aSet.compute_wavelength_grid()
+    names = [str(x) for x in st['atom_names']]
+    assert [m.name for m in spect.models] == names
+    assert np.array_equal(spect.wavelength, st['grid_wavelength']) and list(spect.blueIdx) == list(st['grid_blueIdx'])
+    for k, (t, (a, il, q)) in enumerate(zip(spect.transitions, st['grid_trans_order'])):
+        pre = 'm%d_%s_' % (a, 'line' if il else 'cont')
+        assert (t.atom.name, t.i, t.j) == (names[a], st[pre + 'i'][q], st[pre + 'j'][q])
+        assert np.array_equal(t.wavelength, st['grid_wavelength'][st['grid_blueIdx'][k]:][:st['grid_Nlambda'][k]])
+        assert isinstance(t, AtomicLine) == bool(il) and (il or np.array_equal(t.alpha, st['m%d_cont%d_alpha' % (a, q)]))
+    for la, s in enumerate(spect.activeSet):
+        assert [spect.transitions.index(t) for t in s] == list(np.nonzero(st['grid_active'][:, la])[0])
+    save('live_ref.npz', d)
+
+
 if __name__ == '__main__':
     what = sys.argv[1:] or ['all']
     if 'all' in what:
@@ -539,5 +588,6 @@ if __name__ == '__main__':
         t0 = time.time()
         {'units': gen_units, 'falc_ca': gen_falc_ca, 'falc_cah': gen_falc_cah,
          'falc_ca_vlos': gen_falc_ca_vlos, 'rf': gen_rf, 'falc_c': lambda: gen_falc_multilevel('c'),
-         'falc_fe': lambda: gen_falc_multilevel('fe'), 'falc_mg': lambda: gen_falc_multilevel('mg'), 'falc_all': gen_falc_all, 'rf_inputs': gen_rf_inputs, 'setup': gen_setup}[w]()
+         'falc_fe': lambda: gen_falc_multilevel('fe'), 'falc_mg': lambda: gen_falc_multilevel('mg'), 'falc_all': gen_falc_all, 'rf_inputs': gen_rf_inputs, 'setup': gen_setup,
+         'live_ref': gen_live_ref}[w]()
         print('%s done in %.1fs' % (w, time.time() - t0), flush=True)

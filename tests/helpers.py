@@ -194,3 +194,24 @@ def build_data_fakes(d, s, start_pops=None):
     if 'H' not in eq:
         eq['H'] = FakeState(np.array(d['hGround'])[None], None)
     return atmos, spect, eq, FakeBackground(d)
+
+
+def restore_local_grids(models, s):
+    """DataAtom models (build_data_fakes) back in the state before the reference merges their grids: every transition on
+    its own local grid, continua with their tabulated (or hydrogenic) alpha (s: setup_falc.npz) -> models"""
+    names = [str(x) for x in s['atom_names']]
+    for m in models:
+        a = names.index(m.name)
+        pos = {(int(i), int(j)): q for q, (i, j) in enumerate(zip(s['m%d_line_i' % a], s['m%d_line_j' % a]))}
+        for l in m.lines:
+            l.wavelength = s['m%d_line%d_grid0' % (a, pos[(l.i, l.j)])].copy()
+        cpos = {(int(i), int(j)): q for q, (i, j) in enumerate(zip(s['m%d_cont_i' % a], s['m%d_cont_j' % a]))}
+        for c in m.continua:
+            q = cpos[(c.i, c.j)]
+            c.wavelength, c.alpha = s['m%d_cont%d_grid0' % (a, q)].copy(), s['m%d_cont%d_alpha_grid0' % (a, q)].copy()
+            c.lambdaEdge = float(s['m%d_cont_edge' % a][q])
+            if s['m%d_cont_hydrogenic' % a][q]:
+                c.alpha0, c.minLambda = float(s['m%d_cont_alpha0' % a][q]), float(s['m%d_cont_minLambda' % a][q])
+                lev = lambda k: type('L', (), dict(E_SI=float(s['m%d_lev_E_SI' % a][k]), stage=int(s['m%d_lev_stage' % a][k])))
+                c.iLevel, c.jLevel = lev(c.i), lev(c.j)
+    return models

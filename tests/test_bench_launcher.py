@@ -98,3 +98,29 @@ def test_two_rank_rehearsal_on_one_gpu(which):
         assert len({q['options_signature'] for q in sr['per_rank']}) == 1
         assert max(q['ms_per_step'] for q in sr['per_rank']) == pytest.approx(r['ms_per_step'], rel=1e-9)
         assert 'mapping=ray-serial' in r['config']['runtime_env']['effective_options']
+
+
+def test_dump_outputs_sample_and_files(oracle_lib, tmp_path, monkeypatch):
+    """--dump-outputs on a CPU engine: what the last step left (J, I, n, per-column monitors), all columns while they fit, else
+    one fixed seeded sample of them; float64 files within the limit"""
+    import numpy as np
+    import bench
+    from lightspinner_amd import Engine, fixtures
+    fx = os.path.join(ROOT, 'tests', 'golden', 'falc_ca.npz')
+    prob, _, _ = fixtures.load_problem_npz(fx, phi_compact=False)
+    batch, prof = bench.generate_columns(fx, 0, 12, False)
+    eng = Engine(prob, 12, lib=oracle_lib)
+    bench.load_columns(eng, batch, prof)
+    _, _, dJ, dP = bench.timed_steps(eng, None, 2, 1, lambda: None)
+    full = bench.engine_outputs(eng, dJ, dP)
+    assert np.array_equal(full['columns'], np.arange(12)) and full['J'].shape == (12, prob.Nspect, prob.Nspace)
+    assert np.array_equal(full['monitors'], [dJ, dP])
+    monkeypatch.setattr(bench, 'DUMP_LIMIT_BYTES', 6 * 8 * (prob.Nspect * (prob.Nspace + prob.Nrays) + prob.NLtot * prob.Nspace + 2) + 4096)
+    part = bench.engine_outputs(eng, dJ, dP)
+    assert len(part['columns']) == 6 and np.array_equal(part['columns'], bench.engine_outputs(eng, dJ, dP)['columns'])
+    for k in ('J', 'I', 'n', 'dJ_col', 'dPops_col'):
+        assert np.array_equal(part[k], full[k][part['columns']])
+    bench.write_outputs(str(tmp_path), part)
+    assert sum(os.path.getsize(tmp_path / f) for f in os.listdir(tmp_path)) <= bench.DUMP_LIMIT_BYTES
+    assert all(np.load(tmp_path / (k + '.npy')).dtype == np.float64 for k in part)
+    eng.close()
