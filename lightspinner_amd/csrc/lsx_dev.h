@@ -144,7 +144,7 @@ struct SweepParams {
     const double* bgchi_T;
     const double* bgeta_T;
     const double* bgce_T;       // [col][tile][k][j<L][2]: background opacity and emissivity as PAIRS (round 6: one 16-byte load per lane and depth
-                                // instead of two 8-byte ones in the ray-serial instances; LSX_BG_PAIRS), or nullptr
+                                // instead of two 8-byte ones in the ray-serial instances), or nullptr
     const double* bgxce_T;      // ... and the effective background (pre-pass output) of the ray-serial classes that keep the pre-pass
     const double* bgxchi_T;     // effective background of tiles with fast continua (k_fast_prepass)
     const double* bgxeta_T;
@@ -200,50 +200,35 @@ static LSX_HD inline size_t phi_elem(size_t col, int G, size_t col_stride, size_
 // 1/x: v_rcp_f64 seed (about 2^-26 relative) + one Newton step: relative error <= 4e-15, three instructions instead of
 // the ~12 of an IEEE division.  The reference divides; measured effect on the parity figures against two steps (exact to
 // an ulp): J, I unchanged at 1e-13 / 2e-12, off-diagonal Gamma 2e-13 -> 6e-13 (CaII), 5e-11 -> 9e-11 (Ca+H) -- inside
-// the stated tolerances; -DLSX_NEWTON2 restores the second step.
+// the stated tolerances.
 static __device__ __forceinline__ double rcp(double x)
 {
     double r = __builtin_amdgcn_rcp(x);
     r = fma(fma(-x, r, 1.0), r, r);
-#ifdef LSX_NEWTON2
-    r = fma(fma(-x, r, 1.0), r, r);
-#endif
     return r;
 }
 // d = a * b + c as the three-address VOP3 form.  The compiler prefers v_fmac (d += a * b), which costs an extra
 // v_mov_b64 whenever c must survive (polynomial coefficients, running sums that are read again).
 static __device__ __forceinline__ double fma3(double a, double b, double c)
 {
-#ifndef LSX_NO_FMA3
     double d;
     asm("v_fma_f64 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
     return d;
-#else
-    return fma(a, b, c);
-#endif
 }
 // the same with a wave-uniform second factor (a literal constant: one scalar register pair, no vector registers)
 static __device__ __forceinline__ double fma3s(double a, double b_uniform, double c)
 {
-#ifndef LSX_NO_FMA3
     double d;
     asm("v_fma_f64 %0, %1, %2, %3" : "=v"(d) : "v"(a), "s"(b_uniform), "v"(c));
     return d;
-#else
-    return fma(a, b_uniform, c);
-#endif
 }
 
 // ... and with a wave-uniform addend (Horner steps: the coefficient sits in a scalar register pair)
 static __device__ __forceinline__ double fma3c(double a, double b, double c_uniform)
 {
-#ifndef LSX_NO_FMA3
     double d;
     asm("v_fma_f64 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "s"(c_uniform));
     return d;
-#else
-    return fma(a, b, c_uniform);
-#endif
 }
 
 typedef __attribute__((address_space(3))) double lds_f64;   // LDS pointers carry their address space: ds_ instructions, no flat-pointer checks
@@ -295,22 +280,6 @@ static __device__ __forceinline__ double min_noquiet(double a, double b)
 // for the whole wavefront when no lane is in the middle regime (top / bottom of the atmosphere).
 static __device__ __forceinline__ void w2(double dtau, double& w0, double& w1, const lds_f64* exp2_tab)
 {
-#ifdef LSX_W2_SELECT    // diagnostic variant: round 2's form (the series always, two selects)
-    const bool small = dtau < 5e-4;
-    const bool large = dtau > 50.0;
-    double a0 = 1.0, a1 = 1.0;
-    if (__builtin_amdgcn_ballot_w64(!(small || large)) != 0) {
-        const double dc = min_noquiet(dtau, 700.0);
-        const double e = exp_tab64(-dc, exp2_tab);
-        a0 = 1.0 - e;
-        a1 = a0 - dc * e;
-    }
-    const double t0 = dtau * (1.0 - 0.5 * dtau);
-    const double t1 = (dtau * dtau) * (0.5 - dtau * (1.0 / 3.0));
-    w0 = small ? t0 : a0;
-    w1 = small ? t1 : a1;
-}
-#else
     const bool small = dtau < 5e-4;
     const bool large = dtau > 50.0;
     double a0, a1;
@@ -337,7 +306,6 @@ static __device__ __forceinline__ void w2(double dtau, double& w0, double& w1, c
     w0 = a0;
     w1 = a1;
 }
-#endif
 
 // Weights of the parabolic rule (include/lsx.h, N4): w_n = int_0^dtau t^n e^-t dt, n = 0, 1, 2; same regimes and the same
 // exponential as w2.

@@ -51,9 +51,9 @@ struct FastParams {
     int epi_corr, Nlines;
     const double* fgtab;        // [tile][LSX_FGC_TAB(L)] the column-mapped epilogue's per-tile tables, ready made (lsx_create)
     const double* wphi;         // [col][Nlines][k]
-    // round 6: the column-mapped epilogue forms the Boltzmann factor exp(-hc / k lambda T) from the temperature and the tile's table
-    // (lsx_dev.h, boltzmann_factor: the bits E_T holds) instead of reading the stream: one stream of four less.  nullptr: read E_T
-    // (the fused small-batch launch: a single column is latency bound, not byte bound)
+    // temperature, exp2_tab: unread, the column-mapped epilogue reads the Boltzmann factor from E_T.  Forming it from the temperature
+    // instead was measured in round 6: 0.5 MB per column of C4 traffic less, the call 0.5 % SLOWER (the kernel is a chain of dependent
+    // phases, not a byte mover; profiles/r06_bound_evidence.md 4)
     const double* temperature;  // [col][k]
     const double* exp2_tab;     // the exponential's table (lsx_dev.h, exp_tab64)
 };
@@ -201,19 +201,14 @@ static __device__ __forceinline__ void fast_gamma_cols_rows(const FastParams& f,
     double* sA = sm;                                          // [q][j]{alpha, wlambda}, 0 where the continuum is inactive
     double* sU = sA + (size_t)2 * MAXF * L;                    // [j] 2hc/lambda^3
     double* sLW = sU + L;                                      // [u < 2][j] the linked lines' wavelength weights (0 outside the line)
-    [[maybe_unused]] double* sAE = sLW + 2 * L;                // LSX_EPI_ELANE: [j] -hc / (k lambda), the Boltzmann factor's per-wavelength constant,
-    [[maybe_unused]] double* sET = sAE + L;                    // and [LSX_EXP_TAB] the exponential's table (lsx_plan.h, LSX_FGC_EXTRA)
-    double* sS = sLW + 2 * L + LSX_FGC_EXTRA(L) + (size_t)wv * NST * R * L;     // this wave's streams: [J | Psibar | E | PsiPhi_u][row][j]
+    double* sS = sLW + 2 * L + (size_t)wv * NST * R * L;       // this wave's streams: [J | Psibar | E | PsiPhi_u][row][j]
     // The tile's tables -- cross-section and wavelength weight of every fast continuum (0 where it is not active), 2hc/lambda^3, the
     // linked lines' wavelength weights -- come ready made from lsx_create (f.fgtab, an image of this LDS area per tile): ONE coalesced
     // copy.  (Round 5.  Gathered here from the slot table, the activity table and the atoms' arrays they were a chain of four
     // dependent small loads at the head of every workgroup: profiles/r05/ablation_epilogue_kernel.txt.)
     {
         const double* tab = f.fgtab + (size_t)t * LSX_FGC_TAB(L);
-        const int nA = tl.nF * L, nB = (LSX_EPI_ELANE ? 4 : 3) * L / 2;      // double2 pieces: [q][j]{alpha, wlambda} | u, the two lines' weights (, the Boltzmann constants)
-#if LSX_EPI_ELANE
-        if (f.temperature) for (int e = tid; e < LSX_EXP_TAB; e += NT) sET[e] = f.exp2_tab[e];
-#endif
+        const int nA = tl.nF * L, nB = 3 * L / 2;       // double2 pieces: [q][j]{alpha, wlambda} | u, the two lines' weights
         for (int e = tid; e < nA + nB; e += NT) {       // (the image in memory is laid out for LSX_FGC_MAXF_BIG continua, the LDS area for MAXF)
             const int os = e < nA ? 2 * e : 2 * LSX_FGC_MAXF_BIG * L + 2 * (e - nA), od = e < nA ? 2 * e : 2 * MAXF * L + 2 * (e - nA);
             *reinterpret_cast<double2*>(sm + od) = *reinterpret_cast<const double2*>(tab + os);
@@ -240,22 +235,9 @@ static __device__ __forceinline__ void fast_gamma_cols_rows(const FastParams& f,
         }
         const bool kx = live && 2 * p < tl.nla, ky = live && 2 * p + 1 < tl.nla;
         const size_t o = ((size_t)((size_t)col * f.ntile + t) * Ns + k) * L + 2 * p;
-#ifdef LSX_NT_EPI     // (measured alternative, profiles/r06_bound_evidence.md 1: the epilogue's read-once streams non-temporally)
-        typedef double nt_d2 __attribute__((ext_vector_type(2)));
-        auto ldnt = [](const double* q) __attribute__((always_inline)) { const nt_d2 v = __builtin_nontemporal_load(reinterpret_cast<const nt_d2*>(q)); return make_double2(v.x, v.y); };
-        const double2 vJ = ldnt(f.J_T + o);
-        const double2 a = ldnt(f.Psi2_T + o), b = ldnt(f.Psi2_T + dstride + o);
-#else
         const double2 vJ = *reinterpret_cast<const double2*>(f.J_T + o);
         const double2 a = *reinterpret_cast<const double2*>(f.Psi2_T + o), b = *reinterpret_cast<const double2*>(f.Psi2_T + dstride + o);
-#endif
         double2 vE;
-#if LSX_EPI_ELANE
-        if (f.temperature) {       // (wave-uniform) exp(-hc / k lambda T) of the pair's two wavelengths: the bits k_build_E writes into E_T
-            const double rT = 1.0 / f.temperature[(size_t)col * Ns + k];
-            vE = make_double2(boltzmann_factor(sAE[2 * p], rT, (const lds_f64*)sET), boltzmann_factor(sAE[2 * p + 1], rT, (const lds_f64*)sET));
-        } else
-#endif
         vE = *reinterpret_cast<const double2*>(f.E_T + o);
         double2 vL[NL1];
 #pragma unroll
@@ -263,11 +245,7 @@ static __device__ __forceinline__ void fast_gamma_cols_rows(const FastParams& f,
             vL[u] = zero2;
             if (LINKS && u < nLc) {
                 const double* pp = f.Psi3_T + (size_t)col * f.pp_col_stride + tl.pp_off + (size_t)u * plane + (size_t)k * L + 2 * p;
-#ifdef LSX_NT_EPI
-                const double2 x = ldnt(pp), y = ldnt(pp + pstride);
-#else
                 const double2 x = *reinterpret_cast<const double2*>(pp), y = *reinterpret_cast<const double2*>(pp + pstride);
-#endif
                 vL[u] = make_double2(x.x + y.x, x.y + y.y);
             }
         }

@@ -1515,7 +1515,7 @@ int lsx_create_with_options(const lsx_problem* d, int32_t ncol, int32_t device, 
     TRY(dmalloc(&c->d_wphi, nc * c->Nlines * Ns));
     TRY(dmalloc(&c->d_bgchi, nc * c->til_col));
     TRY(dmalloc(&c->d_bgeta, nc * c->til_col));
-    if (LSX_BG_PAIRS && c->rs_ok) TRY(dmalloc(&c->d_bgce, 2 * nc * c->til_col));      // the same two arrays as pairs, for the folded ray-serial instances
+    if (c->rs_ok) TRY(dmalloc(&c->d_bgce, 2 * nc * c->til_col));      // the same two arrays as pairs, for the folded ray-serial instances
     TRY(dmalloc(&c->d_sca, nc * c->sca_col));
     // (whole column groups: the store interleaves the columns of a group, lsx_dev.h phi_elem)
     const size_t nc_phi = (nc + c->phi_group - 1) / c->phi_group * c->phi_group;
@@ -1750,11 +1750,7 @@ static int enqueue_fs(lsx_ctx* c, bool timed, bool speculative = false)
         ff.bgchi_T = c->d_bgchi; ff.bgeta_T = c->d_bgeta;
         ff.bgxchi_T = c->d_bgxchi; ff.bgxeta_T = c->d_bgxeta; ff.bgxce_T = c->d_bgxce; ff.pairs_out = 0; ff.J_T = c->d_J[c->jcur ^ 1]; ff.Psi2_T = c->d_Psi2;
         ff.Gpart = c->d_Gpart; ff.colmask = c->d_colmask;
-        ff.epi_corr = 0; ff.Nlines = c->Nlines; ff.wphi = c->d_wphi; ff.fgtab = c->d_fgtab;
-        // LSX_EPI_ELANE=1: the column-mapped epilogue forms the Boltzmann factor itself instead of reading the stream -- built and measured
-        // (profiles/r06_bound_evidence.md 4): 0.5 MB per column of C4 traffic less, the call 0.5 % SLOWER (the kernel is a chain of dependent
-        // phases, not a byte mover); off by default
-        ff.temperature = (LSX_ELANE && LSX_EPI_ELANE) ? c->d_temperature : nullptr; ff.exp2_tab = c->d_exp2_tab;
+        ff.epi_corr = 0; ff.Nlines = c->Nlines; ff.wphi = c->d_wphi; ff.fgtab = c->d_fgtab; ff.exp2_tab = c->d_exp2_tab;
     }
     // launch shapes (rows per pass, staged depths, LDS bytes): fixed and checked when the plan was made (lsx_plan.cpp)
     const LaunchShapes& S = c->shapes;
@@ -1898,9 +1894,7 @@ static int enqueue_fs(lsx_ctx* c, bool timed, bool speculative = false)
                 if (!k.tdone) note(hipEventCreate(&k.tdone));
                 if (k.tdone) note(hipEventRecord(k.tdone, st));
             }
-#ifndef LSX_ABL_NO_FAST_GAMMA       // (ablation build, wrong results: what a call costs without the fast-continuum epilogue -- profiles/r05)
             if (!k.fast_tiles.empty() && !epi_in_sweep) launch_fast_gamma(st, k.fast_cols, k.d_fast_cols, k.d_fast_rest, k.fast_rest.size(), epi);
-#endif
             if (fork) {
                 note(hipEventRecord(k.done, st));
                 note(hipStreamWaitEvent(c->stream, k.done, 0));

@@ -22,7 +22,7 @@
 #define LSX_FGC_ROWS 32       // k_fast_gamma_cols: (column, depth) rows per wave
 #define LSX_FGC_MAXF_BIG 48   // ... of the instances for atoms with MORE than LSX_FAST_NQ continua at a wavelength (k_fast_gamma_cols_big: carbon, iron, MgII)
 #define LSX_FGC_LISTS 7       // tile lists of the column-mapped epilogue: [0..2] 0 / 1 / 2 lines fed by linked continua, [3] unused, [4..6] the same, big sets
-#define LSX_FGC_TAB(L) (2 * LSX_FGC_MAXF_BIG * (L) + 4 * (L))   // doubles of a tile's ready-made table (lsx_create): [q][j]{alpha, w} | [j] u | [2][j] line weights | [j] -hc / (k lambda) (round 6: the Boltzmann factor is formed from it)
+#define LSX_FGC_TAB(L) (2 * LSX_FGC_MAXF_BIG * (L) + 4 * (L))   // doubles of a tile's ready-made table (lsx_create): [q][j]{alpha, w} | [j] u | [2][j] line weights | [j] -hc / (k lambda) (unread: the epilogue reads E_T, lsx_fast.h)
 #define LSX_FGC_MAXF 12       // k_fast_gamma_cols: fast continua per tile (sizes its operand table)
 
 // ---- the compiled instances of lsx_sweep_kernel<NPT, NL, NR, SCAL, LK, TOPO> (per-ray slots, lines among them, linked
@@ -53,11 +53,10 @@ inline bool lsx_sweep_instance_exists(int npt, int nl, bool lk, int topo)
 }
 
 // ---- LDS layout of one sweep workgroup (doubles from the start of dynamic LDS), shared by the kernel (offsets) and the plan
-// (bytes to request).  -DLSX_RED_LDS (measured variant, not the product): lane sums of the Gamma integrands through a
-// transposition buffer -- the lanes park their values for lsx_red_steps(npt) depth steps ([step][value][lane], rows padded to
-// 66 doubles: conflict-free 16-byte reads), then every lane adds up one chunk of one row and a short DPP tail finishes: 12 %
-// fewer vector instructions per step, 3-5 % MORE time on C3 (the added LDS round trip lengthens each wave's serial chain;
-// profiles/r03_bound_evidence.md).
+// (bytes to request).  The lane sums of the Gamma integrands are DPP / permlane trees (lsx_sweep.hip); their totals are parked in
+// the `tb` area, [2 waves][2 npt][64], until 64 depths can leave in one store.  Measured and not kept: the sums through a
+// transposition buffer of lsx_red_steps(npt) depth steps, 12 % fewer vector instructions per step, 3-5 % MORE time on C3 (the added
+// LDS round trip lengthens each wave's serial chain; profiles/r03_bound_evidence.md).
 #ifndef LSX_RED_T1
 #define LSX_RED_T1 4
 #endif
@@ -66,21 +65,12 @@ inline bool lsx_sweep_instance_exists(int npt, int nl, bool lk, int topo)
 #endif
 constexpr int lsx_red_steps(int npt) { return npt == 1 ? LSX_RED_T1 : (npt == 2 ? LSX_RED_T2 : 1); }   // depth steps per batch
 constexpr int lsx_red_vectors(int npt) { return npt > 0 ? 2 * npt * lsx_red_steps(npt) : 0; }        // rows per batch: 8, 8, 6, 8
-#ifndef LSX_RED_LDS      // the product's reduction (DPP / permlane trees): [2 waves][2 npt] parked rows of 64 totals instead
 #define LSX_RED_ROW 64
-#undef LSX_RED_T1
-#undef LSX_RED_T2
-#define LSX_RED_T1 1
-#define LSX_RED_T2 1
-#else
-#define LSX_RED_ROW 66
-#endif
 struct SweepLds {
     int rows;        // 64-double rows per wave: level cells, atom cells, one angle-sum row
     int xwg;         // [2][64] cross-wave exchange
     int utab;        // [(Ns + 1)][3 npt + 2] per-depth wave-uniform operands (compile-time slot counts only)
-    int tb;          // [2 waves][vectors][LSX_RED_ROW] transposition buffer
-    int gpk;         // -DLSX_RED_PARK: [2 waves][2 npt][64] totals parked until 64 depths can leave in one store
+    int tb;          // [2 waves][vectors][LSX_RED_ROW]: the parked totals, [2 waves][2 npt][64], at its start
     int ctab;        // [npt][npt - 1][5] slot-pair factors (three and four slots)
     int xrow2;       // [2 waves][npt][64] linked tiles: exchange rows of the Psi* phi sums
     int total;
@@ -93,12 +83,7 @@ constexpr SweepLds lsx_sweep_lds(int npt, bool linked, int Ns, int ncell_lev, in
     l.utab = l.xwg + 2 * LSX_WAVE;
     l.tb = l.utab + (npt >= 0 ? (Ns + 1) * (3 * npt + 2) : 0);
     l.tb += l.tb & 1;                                           // 16-byte aligned rows
-    l.gpk = l.tb + 2 * lsx_red_vectors(npt) * LSX_RED_ROW;
-#if defined(LSX_RED_PARK) && defined(LSX_RED_LDS)
-    l.ctab = l.gpk + (npt > 0 ? 2 * 2 * npt * LSX_WAVE : 0);
-#else
-    l.ctab = l.gpk;
-#endif
+    l.ctab = l.tb + 2 * lsx_red_vectors(npt) * LSX_RED_ROW;
     l.xrow2 = l.ctab + (npt >= 3 ? npt * (npt - 1) * 5 : 0);
     l.total = l.xrow2 + (linked && npt > 0 ? 2 * npt * LSX_WAVE : 0);
     return l;
@@ -164,7 +149,7 @@ inline bool lsx_rsp_instance_exists(int npt, int nl, bool lk, int topo)
 // depth the table holds a third kind of block, [c][3] = n_i, n_j nStar_i / nStar_j, nStar_i / nStar_j, the row of a tile with nF fast
 // continua is 16 (npt + 1 + nF) doubles (two elements per lane: at most 128), and per (wavelength, depth) the lane needs two fused
 // multiply-adds per continuum: chi += sum_q alpha_q n_i,q - E sum_q alpha_q (n_j nsr)_q, eta += (2hc/lambda^3) E sum_q alpha_q (n_j nsr)_q,
-// E = exp(-hc / k lambda T): round 5 the tile's Boltzmann stream, round 6 formed in the lane from the row's 1 / T (LSX_ELANE below).
+// E = exp(-hc / k lambda T): round 5 the tile's Boltzmann stream, round 6 formed in the lane from the row's 1 / T (LSX_RS_GEO below).
 // No pre-pass launch, no effective-background streams for those classes.
 // ... and their GAMMA INTEGRANDS (EPI instances; what k_fast_gamma_cols did, rh_method.py:652, 677-681 for a ray-independent
 // transition): the wave that visits a depth SECOND has the total mean intensity there; it also fetches the first visitor's half of
@@ -178,17 +163,8 @@ inline bool lsx_rsp_instance_exists(int npt, int nl, bool lk, int topo)
 #define LSX_RS_FOLD_ROW_MAX 128         // doubles of a folded row: two elements per lane
 // doubles per column of a geometry row: the half length of the interval behind the ray, the scattering coefficient and (round 6)
 // 1 / T: the Boltzmann factor exp(-hc / k lambda T) of the continua (rh_method.py:453) is formed in the lane from it instead of being
-// read as a stream by both directions (LSX_ELANE=0: the stream, round 5's form)
-#ifndef LSX_ELANE
-#define LSX_ELANE 1
-#endif
-#define LSX_RS_GEO (LSX_ELANE ? 3 : 2)
-#ifndef LSX_BG_PAIRS
-#define LSX_BG_PAIRS 1       // the ray-serial instances read background chi / eta as one 16-byte pair per lane and depth (lsx_dev.h, bgce_T / bgxce_T)
-#endif
-#ifndef LSX_EPI_ELANE
-#define LSX_EPI_ELANE 0      // the same in the column-mapped fast-continuum epilogue: a measured alternative (lsx_hip.hip, enqueue_fs)
-#endif
+// read as a stream by both directions (round 5's form)
+#define LSX_RS_GEO 3
 // A row is made of SEGMENTS -- one per per-ray slot, the geometry, one per folded continuum --, each [column][3] = 15 doubles padded to
 // LSX_RS_SEG = 16 (round 6): a lane then fetches TWO consecutive elements of the row with one 16-byte load (64 lanes: the 128 doubles a
 // folded row may have), where it used to fetch elements e and 64 + e with two loads -- one request per step less in every folded
@@ -201,11 +177,8 @@ constexpr int lsx_rs_row_doubles(int npt, int nF = 0) { return LSX_RS_SEG * (npt
 // table are laid out for the class's largest tile rounded up to a multiple of four
 // (nor of the unfactored two-line instance with linked continua: it reads the pre-pass's correction streams)
 // (round 6: with the Boltzmann factor formed in the lane -- one operand stream less -- the two-line instances with a known relation fit
-// the fold too: 255 registers, no scratch; LSX_FOLD_TWOLINE=0 restores round 5's list, in which they kept the pre-pass)
-#ifndef LSX_FOLD_TWOLINE
-#define LSX_FOLD_TWOLINE LSX_ELANE
-#endif
-constexpr bool lsx_rs_fold_instance_exists(int npt, bool lk, int topo) { return (LSX_FOLD_TWOLINE || !(npt == 2 && !lk && topo != 0)) && !(npt == 2 && lk && topo == 0); }
+// the fold too: 255 registers, no scratch; in round 5 they kept the pre-pass)
+constexpr bool lsx_rs_fold_instance_exists(int npt, bool lk, int topo) { return !(npt == 2 && lk && topo == 0); }
 constexpr int lsx_rs_fold_pad(int nF) { return (nF + 3) & ~3; }
 constexpr int lsx_rs_row_pitch(int npt, int nF = 0) { return (lsx_rs_row_doubles(npt, lsx_rs_fold_pad(nF)) + 1) & ~1; }
 // doubles per column group of the table: Ntrans blocks of (Nspace + 1) rows of 15, the geometry block of (Nspace + 1) rows of 10,
@@ -363,9 +336,6 @@ inline int lkclass(const DevTile& tl)
 inline int fgc_list(const DevTile& tl) { return lkclass(tl) + (tl.fast_simple == 3 ? 4 : 0); }
 inline int fgc_lines(int v) { return kLkLines[v & 3]; }
 // LDS of a workgroup of NW waves of the column-mapped epilogue: tables for MAXF continua, NW x (3 + lines) streams of LSX_FGC_ROWS rows
-// (LSX_EPI_ELANE = 1, a measured alternative: + the Boltzmann constants of the tile's wavelengths and the exponential's table -- the kernel
-// then forms exp(-hc / k lambda T) itself; LSX_FGC_EXTRA: those doubles)
-#define LSX_FGC_EXTRA(L) (LSX_EPI_ELANE ? (L) + LSX_EXP_TAB : 0)
-inline size_t fgc_lds_bytes(int L, int maxf, int nw, int lines) { return ((size_t)2 * maxf * L + (size_t)3 * L + LSX_FGC_EXTRA(L) + (size_t)nw * (3 + lines) * LSX_FGC_ROWS * L) * sizeof(double); }
+inline size_t fgc_lds_bytes(int L, int maxf, int nw, int lines) { return ((size_t)2 * maxf * L + (size_t)3 * L + (size_t)nw * (3 + lines) * LSX_FGC_ROWS * L) * sizeof(double); }
 
 } // namespace lsxd

@@ -378,24 +378,6 @@ __device__ __forceinline__ void sweep_tile(const SweepParams& p, const int vb, c
 
     auto stream_loads = [&](int kk, double& bc, double& be, double& jdv, double (&v)[NS], double& Ev, double (&cr)[NLK][3]) {
         const unsigned kko = (unsigned)(kk * L + j) * 8u;
-#ifdef LSX_ABL_NOLOAD     // diagnostic build (profiles/ablate.sh): what the step costs without its HBM streams; results are meaningless
-        {
-            const double f = 1.0 + 1e-3 * (double)(kko & 1023u);
-            jdv = 1e-9 * f; bc = 1e-6 * f; be = 1e-15 * f;
-            if constexpr (STATIC) {
-#pragma unroll
-                for (int u = 0; u < NL; ++u) v[u] = 1e-12 * f;
-                if constexpr (HASC) Ev = 0.5 * f;
-                if constexpr (LK) {
-#pragma unroll
-                    for (int u = 0; u < NL; ++u)
-#pragma unroll
-                        for (int q = 0; q < NCR; ++q) cr[u][q] = 1e-20 * f;
-                }
-            }
-            return;
-        }
-#endif
         jdv = at(Jdag, kko);
         bc = at(bgchi, kko);
         be = at(bgeta, kko);
@@ -414,31 +396,14 @@ __device__ __forceinline__ void sweep_tile(const SweepParams& p, const int vb, c
     };
     if constexpr (STATIC) stream_loads(kS, n_bc, n_be, n_jd, n_sv, n_E, n_cr);
 
-#ifndef LSX_RED_LDS     // lane reduction by DPP / permlane trees, totals parked in 64-entry LDS rows (-DLSX_RED_LDS: the measured alternative)
-    // Gamma totals wait in LDS, one 64-entry row per (slot, entry) and wave, until 64 depths can leave in one store.
+    // lane reduction by DPP / permlane trees (lsx_dev.h); the Gamma totals wait in LDS, one 64-entry row per (slot, entry) and wave,
+    // until 64 depths can leave in one store (lsx_plan.h, lsx_sweep_lds).
     // The lanes that hold totals after a reduction (31 / 63, or 15 / 47 / 31 / 63) each own one row.
     lds_f64* const gpk = etab + lay.tb + (size_t)dir * (2 * NS) * LSX_WAVE;
     const bool own_pair = lane == 31 || lane == 63, own_quad = (lane & 15) == 15;
     const int row_pair = (lane >> 5) * LSX_WAVE;                                   // 31 -> row 0, 63 -> row 1
     const int row_quad = ((((lane >> 4) & 1) << 1) | (lane >> 5)) * LSX_WAVE;      // 15 -> 0, 47 -> 1, 31 -> 2, 63 -> 3
 
-#else
-    // Lane sums of the Gamma integrands: the lanes park their 2 NPT values of RT consecutive depth steps in this wave's
-    // transposition buffer tb[step in batch][value][lane] (rows of LSX_RED_ROW doubles); at the end of a batch every lane adds
-    // up one chunk of one row and a DPP tail over the chunk's lanes finishes (lsx_plan.h).  The first lane of a row's group
-    // stores the total: each batch leaves as ONE store instruction with one lane per (depth, value).
-    constexpr int RT = lsx_red_steps(NPT > 0 ? NPT : 1), NV = 2 * NS, RV = NV * RT;     // RV rows per batch (<= 8)
-    constexpr int RVP = RV <= 4 ? 4 : 8, LPV = LSX_WAVE / RVP;                           // lanes per row; doubles per lane = RVP
-    lds_f64* const tb = etab + lay.tb + (size_t)dir * RV * LSX_RED_ROW;
-#ifdef LSX_RED_PARK
-    lds_f64* const gpk = etab + lay.gpk + (size_t)dir * (2 * NS) * LSX_WAVE;
-#endif
-    const int rv_raw = lane / LPV, rc = lane - rv_raw * LPV;
-    const int rv = rv_raw < RV ? rv_raw : RV - 1;                                         // (RV = 6: the last two groups idle)
-    const int rt = rv / NV, rq = rv - rt * NV;                                            // step in batch, value index (2 slot + entry)
-    const bool r_own = rc == 0 && rv_raw < RV;
-
-#endif
     // A sweep runs in three phases with a fixed set of memory operations each, so the compiler's wait counts are
     // exact and neither a store acknowledgement nor the half-J read-back is waited for inside a step:
     //   phase 0: this wave is the first visitor of its depths (stores its half of J)
@@ -556,14 +521,9 @@ __device__ __forceinline__ void sweep_tile(const SweepParams& p, const int vb, c
             Lam = 0.0;
         } else {
             const double dtau = (chi_prev + chiTot) * hdzm;
-#ifdef LSX_RCP2        // diagnostic variant: one reciprocal per division
-            rchi = rcp(chiTot);
-            const double rdt = rcp(dtau);
-#else
             const double rcd = rcp(chiTot * dtau);
             rchi = rcd * dtau;
             const double rdt = rcd * chiTot;
-#endif
             S = etaTot * rchi;                          // :632
             const double dS = (S_prev - S) * rdt;
             // formal_solver.py:138-139: the end point re-uses the PREVIOUS interval's w and
@@ -656,11 +616,7 @@ __device__ __forceinline__ void sweep_tile(const SweepParams& p, const int vb, c
                 const SlotS sl = load_slot(slots + u, Ns);
                 const bool line = u < NL;
                 const double Vij = line ? sl.cB * spv[u] : alv[u];
-#ifndef LSX_RED_LDS
                 const double wt = line ? wlv[u] * tk[3 * u + 2] : wlv[u];         // :451 (lines: x wphi), :455, :665
-#else
-                const double wt = wlv[u];         // :455, :665; the lines' wphi (:451) is wave-uniform: applied to the lane sum
-#endif
                 // linked continua add their ray-independent share to the line's atom.eta, atom.chi[i], atom.chi[j]
                 // (x + 0.0 is not x to the compiler: the corrections are added only where the instance has them)
                 const bool lkl = LK && line;
@@ -718,7 +674,6 @@ __device__ __forceinline__ void sweep_tile(const SweepParams& p, const int vb, c
                     w2v[u] = wt * (Vij * Ieff);                                                          // :680
                 }
             }
-#ifndef LSX_RED_LDS
             // the totals of step s are parked in entry (s mod 64) of per-(slot, entry) LDS rows and leave as one
             // 64-wide store every 64 steps: no store (and no store acknowledgement to wait for) inside a step
             const int sl64 = s & 63;
@@ -744,53 +699,6 @@ __device__ __forceinline__ void sweep_tile(const SweepParams& p, const int vb, c
                     for (int q = 0; q < 2 * NPT; ++q) gpart[(q * 2 + dir) * Ns + ks] = gpk[q * LSX_WAVE + lane];
                 }
             }
-#else
-            if constexpr (NPT >= 1) {
-                const int pos = s & (RT - 1);
-                lds_f64* const tbw = tb + pos * NV * LSX_RED_ROW + lane;
-#pragma unroll
-                for (int u = 0; u < NPT; ++u) {
-                    tbw[(2 * u) * LSX_RED_ROW] = w1[u];
-                    tbw[(2 * u + 1) * LSX_RED_ROW] = w2v[u];
-                }
-                if (pos == RT - 1 || s == Ns - 1) {
-                    __builtin_amdgcn_wave_barrier();
-                    // 16-byte reads (ds_read_b128: 64 banks, conflict free on rows of LSX_RED_ROW doubles; the 8-byte forms
-                    // would put a 16-lane group on two banks)
-                    typedef double lds_pair __attribute__((ext_vector_type(2)));
-                    const auto* src = (const __attribute__((address_space(3))) lds_pair*)(tb + rv * LSX_RED_ROW + rc * RVP);   // 16-byte aligned (lsx_sweep_lds)
-                    lds_pair v2 = src[0];
-                    double acc = v2.x + v2.y;
-#pragma unroll
-                    for (int e = 1; e < RVP / 2; ++e) { v2 = src[e]; acc += v2.x + v2.y; }
-                    acc += dpp_f64<0xB1, 0xf>(acc);                          // quad_perm [1,0,3,2]
-                    acc += dpp_f64<0x4E, 0xf>(acc);                          // quad_perm [2,3,0,1]
-                    acc += dpp_f64<0x141, 0xf>(acc);                         // row_half_mirror: 8-lane sums
-                    if constexpr (LPV == 16) acc += dpp_f64<0x140, 0xf>(acc); // row_mirror: 16-lane sums
-                    const int kt = kS + dk * (s - pos + rt);                 // the depth this lane's row belongs to
-                    if (r_own && rt <= pos) {
-                        // lines: x wphi of that depth (rh_method.py:451); continua (:455) carry their whole weight in wlv
-                        const double wn = (rq >> 1) < NL ? utab[kt * TR + 3 * (rq >> 1) + 2] : 1.0;
-#ifdef LSX_RED_PARK
-                        gpk[rq * LSX_WAVE + ((s - pos + rt) & 63)] = acc * wn;
-#else
-                        gpart[(rq * 2 + dir) * Ns + kt] = acc * wn;
-#endif
-                    }
-                    __builtin_amdgcn_wave_barrier();
-#ifdef LSX_RED_PARK
-                    const int sl64 = s & 63;
-                    if (sl64 == 63 || s == Ns - 1) {
-                        const int ks = kS + dk * (s - sl64 + lane);         // the depth parked in entry `lane` of every row
-                        if (lane <= sl64) {
-#pragma unroll
-                            for (int q = 0; q < 2 * NPT; ++q) gpart[(q * 2 + dir) * Ns + ks] = gpk[q * LSX_WAVE + lane];
-                        }
-                    }
-#endif
-                }
-            }
-#endif
         } else {
             for (int u = 0; u < nP; ++u) {
                 const SlotS sl = load_slot(slots + u, Ns);
@@ -1516,12 +1424,9 @@ lsx_sweep_kernel(const SweepParams p)
 // stack per lane for the callee-saved registers), and the scalar registers the instances compete for spill into vector lanes
 // (383 `v_writelane`s, no memory) -- at the one or two waves per SIMD this kernel runs with there are vector registers to spare.
 // Measured on the single FALC column: formal solution 83.6 -> 78.8 us, MALI iteration 79.0 -> 74.4 us
-// (profiles/r04/c2_instances_inlined.txt).  LSX_TILE_CALL='__attribute__((noinline))' builds the called form.
-#ifndef LSX_TILE_CALL
-#define LSX_TILE_CALL __attribute__((always_inline))
-#endif
+// (profiles/r04/c2_instances_inlined.txt).
 template <int NPT, int NL, int NR, bool SCAL, bool LK, int TOPO = 0>
-__device__ LSX_TILE_CALL void sweep_tile_call(const SweepParams& p, const int vb, const int tile_id)
+__device__ __attribute__((always_inline)) void sweep_tile_call(const SweepParams& p, const int vb, const int tile_id)
 {
     sweep_tile<NPT, NL, NR, SCAL, LK, TOPO>(p, vb, tile_id);
 }

@@ -53,27 +53,12 @@ __device__ __forceinline__ double& at(double* base, unsigned byte_off)
 // cache-policy hints (round 6; profiles/r06_bound_evidence.md 1).  The line profiles -- read exactly once per call, the largest stream --
 // are requested non-temporally (global_load ... nt): FETCH_SIZE does not move (the partner wave's re-reads are 100 us away, far beyond
 // any cache), but the profile bytes no longer wash through the CU's vector cache, where the 96-byte rows of the other streams share
-// their 128-byte lines from one depth to the next: C3 -4 % (three boxes: -3, -6, -4), C4 -0.7 %.  LSX_NT_PHI=0: plain loads.
-// Measured and NOT kept: the ray-independent streams non-temporally too (LSX_NT_BG: C3 +8 %, C4 +3.5 %: their lines ARE shared between
-// consecutive depths), non-temporal stores of the sums and slabs (LSX_NT_ST: C4 +8 %: partial lines past the L2's write combining)
-#ifndef LSX_NT_PHI
-#define LSX_NT_PHI 1
-#endif
+// their 128-byte lines from one depth to the next: C3 -4 % (three boxes: -3, -6, -4), C4 -0.7 %.
+// Measured and NOT kept: the ray-independent streams non-temporally too (C3 +8 %, C4 +3.5 %: their lines ARE shared between
+// consecutive depths), non-temporal stores of the sums and slabs (C4 +8 %: partial lines past the L2's write combining)
 __device__ __forceinline__ double ld_once(const double* base, unsigned byte_off)
 {
-#if LSX_NT_PHI
     return __builtin_nontemporal_load(reinterpret_cast<const double*>(reinterpret_cast<const char*>(base) + byte_off));
-#else
-    return at(base, byte_off);
-#endif
-}
-__device__ __forceinline__ void st_once(double* base, unsigned byte_off, double v)
-{
-#ifdef LSX_NT_ST
-    __builtin_nontemporal_store(v, reinterpret_cast<double*>(reinterpret_cast<char*>(base) + byte_off));
-#else
-    at(base, byte_off) = v;
-#endif
 }
 __device__ __forceinline__ double nanmax(double a, double b) { return (a != a || b != b) ? __builtin_nan("") : fmax(a, b); }
 
@@ -118,12 +103,6 @@ lsx_sweep_rs_kernel(const SweepParams p)
     // correction slots) and these instances read NO correction streams: two loads per line, wavelength and depth less, and the
     // pre-pass writes none.  (The unfactored instance <2,2,true,0> applies them ray by ray, like the one-ray-per-lane kernels.)
     constexpr bool CORR = LK && !FACT;
-    // a second depth of stream prefetch (a third operand set) where the register file has room for it: at most one per-ray slot
-#if defined(LSX_RS_PF2)
-    constexpr bool PF2 = !PAR && NPT <= LSX_RS_PF2;
-#else
-    constexpr bool PF2 = false;
-#endif
     const int lane = threadIdx.x & (LSX_WAVE - 1);
     const int dir = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // 0: down (toFrom False), 1: up (True)
     lds_f64* const red = etab + LSX_EXP_TAB + (size_t)dir * (NV + 1) * RROW;   // this wave's reduction rows (+ one for dJ)
@@ -283,14 +262,10 @@ lsx_sweep_rs_kernel(const SweepParams p)
 #pragma unroll
                 for (int i = 0; i < CH; ++i) { SA = fma(a[i], x[i], SA); SB = fma(a[i], y[i], SB); }
             };
-#ifdef LSX_ABL_FOLD_NOCHUNK
-            SA = al[0]; SB = fr[0];                    // ablation build (wrong results): no sums over the continua
-#else
             chunk(0);
             if constexpr (CH == 2) { if (nF > 2) chunk(2); }
             if (nF > 4) { chunk(4); if constexpr (CH == 2) { if (nF > 6) chunk(6); } }
             if (nF > 8) { chunk(8); if constexpr (CH == 2) { if (nF > 10) chunk(10); } }
-#endif
             const double EB = E * SB;
             chi += SA - EB;
             eta = fma(ula, EB, eta);
@@ -301,25 +276,17 @@ lsx_sweep_rs_kernel(const SweepParams p)
     const size_t til_col = (size_t)ntile * Ns * LW;
     const size_t tb0 = ((size_t)col0 * ntile + tile_id) * Ns * LW;
     const unsigned o_til = (unsigned)((size_t)cc * til_col * 8u) + (unsigned)j * 8u;           // + k * LW * 8
-    const double* __restrict__ bgchi = ((nF > 0 && !FOLD) ? p.bgxchi_T : p.bgchi_T) + tb0;      // (FOLD: the plain background; see fast_fold)
-    const double* __restrict__ bgeta = ((nF > 0 && !FOLD) ? p.bgxeta_T : p.bgeta_T) + tb0;
-    // ... read as (chi, eta) pairs, ONE 16-byte load per lane and depth (lsx_dev.h, bgce_T / bgxce_T; round 6: the same bytes in one
-    // request less per step: C4 -2 %, profiles/r06_bound_evidence.md 6 -- what a wave waits for is its requests, not their bytes)
-    constexpr bool BGP = LSX_BG_PAIRS != 0;
-    [[maybe_unused]] const double* __restrict__ bgce = BGP ? ((nF > 0 && !FOLD) ? p.bgxce_T : p.bgce_T) + 2 * tb0 : nullptr;
+    // the background (FOLD: the plain one; see fast_fold) read as (chi, eta) pairs, ONE 16-byte load per lane and depth (lsx_dev.h,
+    // bgce_T / bgxce_T; round 6: the same bytes in one request less per step: C4 -2 %, profiles/r06_bound_evidence.md 6 -- what a wave
+    // waits for is its requests, not their bytes)
+    const double* __restrict__ bgce = ((nF > 0 && !FOLD) ? p.bgxce_T : p.bgce_T) + 2 * tb0;
     const double* __restrict__ Jdag = p.Jdag_T + tb0;
     double* __restrict__ Jnew = p.Jnew_T + tb0;
     double* __restrict__ psibar = p.Psi2_T + ((size_t)dir * p.ncol * ntile) * Ns * LW + tb0;
-    [[maybe_unused]] const double* __restrict__ Eb = p.E_T + tb0;      // (LSX_ELANE=0 and the ablation builds: the Boltzmann factor as a stream)
     // the line-profile store interleaves the columns of a group inside every block row (lsx_dev.h, phi_elem): with G = NC the five
     // columns of this wavefront are ONE group, and row x of a block is one contiguous run [c < NC][l < len] for the whole wavefront
     const int PG = p.phi_G;                                          // NC, or 1: the plain per-column store (LSX_PHI_GROUP=1)
     const double* __restrict__ phi0 = p.phi_T + (size_t)col0 * p.phi_col_stride;
-#ifdef LSX_ABL_PHI_ONECOL
-    const int cphi = 0;              // ablation build (wrong results): the five columns of a wavefront read the FIRST column's profiles
-#else
-    const int cphi = cc;
-#endif
     const double* __restrict__ corr = CORR ? p.corr_T + (size_t)col0 * p.corr_col_stride + tilep->corr_off : nullptr;
     const unsigned o_corr = CORR ? (unsigned)((size_t)cc * p.corr_col_stride * 8u) + (unsigned)j * 8u : 0u;
     double* __restrict__ ppsum = LK ? p.Psi3_T + ((size_t)dir * p.ncol + col0) * p.pp_col_stride + tilep->pp_off : nullptr;
@@ -334,22 +301,14 @@ lsx_sweep_rs_kernel(const SweepParams p)
     // the Boltzmann factor of the tile's continua at depth row v (rh_method.py:453), formed from the row's 1 / T (lsx_dev.h,
     // boltzmann_factor; the stream E_T holds the same bits for the kernels that read it)
     const double aE = boltzmann_lane_constant(wav);
-    auto E_of = [&](const int v, const double E_stream) __attribute__((always_inline)) {
-#if LSX_ELANE
+    auto E_of = [&](const int v) __attribute__((always_inline)) {
         if constexpr (HASC || FOLD) return boltzmann_factor(aE, ring_row(v)[lcg + 2], etab);
         else return 0.0;
-#else
-        return E_stream;
-#endif
     };
     // angle quadrature: wave-uniform
     // two-slot instances: the ten quadrature constants live in LDS behind the parked totals and are read where they are used
     // (broadcast reads with immediate offsets): twenty vector registers less in the instances that sit at the 256-register limit
-    #ifdef LSX_RS_PF2_QLDS
-    constexpr bool QLDS = NPT >= 2 || (PAR && LSX_RSP_WPE >= 2) || (PF2 && NPT >= 1);
-#else
     constexpr bool QLDS = NPT >= 2 || (PAR && LSX_RSP_WPE >= 2) || (FOLD && NPT == 0);      // (the folded continuum instance: three waves per SIMD)
-#endif
     lds_f64* const qtab = ring_end + (size_t)2 * NC * NV * lsx_rs_park(NPT, PAR || EPI);
     if (QLDS && threadIdx.x < 2 * NR) qtab[threadIdx.x] = threadIdx.x < NR ? LSX_CONST(double, p.zmu)[threadIdx.x] : LSX_CONST(double, p.wmuh)[threadIdx.x - NR];
     double zmu_r[NR], wmuh_r[NR];
@@ -377,9 +336,6 @@ lsx_sweep_rs_kernel(const SweepParams p)
         if (l >= 0 && l < slots[u].Nlam && p.active[slots[u].trans * Nspect + la] != 0) pact |= 1u << u;
     }
     unsigned phi_o[NS], phi_k[NS], phi_m[NS];       // lines: byte offset of (depth 0, ray 0), per depth, per ray
-#if defined(LSX_ABL_PHI_WIDE) || defined(LSX_ABL_PHI_PAIRS)
-    unsigned phi_w[NS];
-#endif
     double wlam[NS], alv[NS], cB[NS], Vc[NS], Uc[NS];
 #pragma unroll
     for (int u = 0; u < NPT; ++u) {
@@ -394,15 +350,9 @@ lsx_sweep_rs_kernel(const SweepParams p)
         // column's own base + x len + l.  A lane outside the line's range reads a zero pad at every depth and ray: the last
         // element of the group (of its column)
         const long xl0 = (long)slots[u].base + (compact ? 0L : (long)dir * Ns * NR * len);
-        const long e0 = !line ? 0L : PG > 1 ? (a ? (long)PG * xl0 + (long)cphi * len + lb : (long)PG * p.phi_col_stride - 1)
-                                            : (long)cphi * p.phi_col_stride + (a ? xl0 + lb : (long)p.phi_col_stride - 1);
+        const long e0 = !line ? 0L : PG > 1 ? (a ? (long)PG * xl0 + (long)cc * len + lb : (long)PG * p.phi_col_stride - 1)
+                                            : (long)cc * p.phi_col_stride + (a ? xl0 + lb : (long)p.phi_col_stride - 1);
         phi_o[u] = (unsigned)(e0 * 8);
-#if defined(LSX_ABL_PHI_WIDE) || defined(LSX_ABL_PHI_PAIRS)
-        // ablation build (wrong results; profiles/r06_bound_evidence.md 6): the five rays' profile values of a lane as THREE loads (16 + 16 + 8
-        // bytes) at lane-contiguous 40-byte pieces of the same 2400-byte region the five 480-byte rows of (direction, depth) occupy --
-        // what a [column][wavelength][ray] order of the block rows would cost, before anybody changes the layout
-        phi_w[u] = (line && a && !compact && PG > 1) ? (unsigned)(((long)cphi * len + lb) * 32) : 0u;
-#endif
         phi_k[u] = (line && a) ? (unsigned)(PG * (compact ? 1 : NR) * len * 8) : 0u;
         phi_m[u] = (line && a && !compact) ? (unsigned)(PG * len * 8) : 0u;
         wlam[u] = (a && act) ? (4.0 * kPi) * p.wl[slots[u].wl_off + l] : 0.0;   // :451/:455, :665 without the angle weight
@@ -416,76 +366,22 @@ lsx_sweep_rs_kernel(const SweepParams p)
 #endif
     // ---- one depth's operands ------------------------------------------------------------------------------------------
     struct Ops {
-        double bc, be, jd, E;
+        double bc, be, jd, E;                // (E: 0, unread -- E_of forms the Boltzmann factor; without the field the compiler assigns the
+                                             // registers of <0, 0, false, 0> differently)
         double ph[NS][NR];                   // line profile per ray
         double cr[CORR ? NLK : 1][CORR ? 3 : 1];   // <2,2,true,0>: the continua's share of atom.eta, atom.chi[i], atom.chi[j]
     };
     auto load_ops = [&](int kk, Ops& o) __attribute__((always_inline)) {
-#ifdef LSX_ABL_NOLOAD
-        // ablation build (profiles/r03_bound_evidence.md): every depth gets the operands of the middle one, fetched once; the
-        // values pass through an opaque move so that nothing computed from them leaves the loop
-        kk = Ns / 2;
-#endif
-#ifdef LSX_ABL_SHARED_READS
-        // ablation build (wrong results; profiles/r06_bound_evidence.md 5): the up-going wave reads the ray-independent streams at the depth
-        // its partner is reading at the same moment -- what a call would cost if both directions of a column could share those reads
-        const unsigned kt = o_til + (unsigned)((dir ? Ns - 1 - kk : kk) * LW) * 8u;
-#else
         const unsigned kt = o_til + (unsigned)(kk * LW) * 8u;
-#endif
-#ifdef LSX_NT_BG      // (measured alternative: the ray-independent streams non-temporally too)
-        o.jd = ld_once(Jdag, kt);
-        o.bc = ld_once(bgchi, kt);
-        o.be = ld_once(bgeta, kt);
-#else
         o.jd = at(Jdag, kt);
-        if constexpr (BGP) {
-            typedef double bg_pair __attribute__((ext_vector_type(2)));
-            const bg_pair v = *reinterpret_cast<const bg_pair*>(reinterpret_cast<const char*>(bgce) + 2u * kt);
-            o.bc = v.x; o.be = v.y;
-        } else {
-            o.bc = at(bgchi, kt);
-            o.be = at(bgeta, kt);
-        }
-#endif
+        typedef double bg_pair __attribute__((ext_vector_type(2)));
+        const bg_pair bg = *reinterpret_cast<const bg_pair*>(reinterpret_cast<const char*>(bgce) + 2u * kt);
+        o.bc = bg.x; o.be = bg.y;
         o.E = 0.0;
-#ifdef LSX_ABL_FOLD_NOE
-        if constexpr (HASC) o.E = at(Eb, kt);          // ablation build (wrong results): the folded instances do not read the Boltzmann stream
-        else if constexpr (FOLD) o.E = 0.5;
-#elif !LSX_ELANE
-        if constexpr (HASC || FOLD) o.E = at(Eb, kt);
-#endif
-#if defined(LSX_ABL_PHI_PAIRS)
-        // ablation build (wrong results; profiles/r06_bound_evidence.md 6): the rays' profile values as (ray 0, ray 1), (ray 2, ray 3) PAIRS and
-        // ray 4 -- two 16-byte loads and one 8-byte load whose lanes stay contiguous (960 / 960 / 480 bytes per wave) over the bytes rows
-        // 0-1, 2-3 and 4 occupy today: what a [ray pair][column][wavelength][2] order of the block rows would cost
-        static_assert(NR == 5, "ablation: five rays");
-#pragma unroll
-        for (int u = 0; u < NL; ++u) {
-            typedef double ph2 __attribute__((ext_vector_type(2)));
-            const unsigned o0 = phi_o[u] + (unsigned)kk * phi_k[u];
-            // + (c len + l) 8: the lane's piece doubles; a lane outside the line reads the group's last element: its pair ends there
-            const char* q = reinterpret_cast<const char*>(phi0) + o0 + phi_w[u] / 4u - (phi_m[u] ? 0u : 8u);
-            const ph2 v0 = __builtin_nontemporal_load(reinterpret_cast<const ph2*>(q)), v1 = __builtin_nontemporal_load(reinterpret_cast<const ph2*>(q + 2u * phi_m[u]));
-            o.ph[u][0] = v0.x; o.ph[u][1] = v0.y; o.ph[u][2] = v1.x; o.ph[u][3] = v1.y;
-            o.ph[u][4] = ld_once(phi0, o0 + 4u * phi_m[u]);
-        }
-#elif defined(LSX_ABL_PHI_WIDE)
-        static_assert(NR == 5, "ablation: five rays");
-#pragma unroll
-        for (int u = 0; u < NL; ++u) {
-            typedef double ph2 __attribute__((ext_vector_type(2)));
-            const char* q = reinterpret_cast<const char*>(phi0) + (phi_o[u] + (unsigned)kk * phi_k[u] + phi_w[u]);
-            const ph2 v0 = __builtin_nontemporal_load(reinterpret_cast<const ph2*>(q)), v1 = __builtin_nontemporal_load(reinterpret_cast<const ph2*>(q + 16));
-            o.ph[u][0] = v0.x; o.ph[u][1] = v0.y; o.ph[u][2] = v1.x; o.ph[u][3] = v1.y;
-            o.ph[u][4] = __builtin_nontemporal_load(reinterpret_cast<const double*>(q + 32));
-        }
-#else
 #pragma unroll
         for (int u = 0; u < NL; ++u)
 #pragma unroll
             for (int m = 0; m < NR; ++m) o.ph[u][m] = ld_once(phi0, phi_o[u] + (unsigned)kk * phi_k[u] + (unsigned)m * phi_m[u]);
-#endif
         if constexpr (CORR) {
             const unsigned kq = o_corr + (unsigned)(kk * LW) * 8u;
 #pragma unroll
@@ -493,19 +389,12 @@ lsx_sweep_rs_kernel(const SweepParams p)
 #pragma unroll
                 for (int q = 0; q < NCR; ++q) o.cr[u][q] = at(corr, (unsigned)((3 * u + q) * plane) * 8u + kq);
         }
-#ifdef LSX_ABL_NOLOAD
-        asm volatile("" : "+v"(o.jd), "+v"(o.bc), "+v"(o.be), "+v"(o.E));
-#pragma unroll
-        for (int u = 0; u < NL; ++u)
-#pragma unroll
-            for (int m = 0; m < NR; ++m) asm volatile("" : "+v"(o.ph[u][m]));
-#endif
     };
     // total opacity of ray m from one depth's operands (rh_method.py:613, 279-285)
     auto chi_of = [&](const Ops& o, int v, int m) __attribute__((always_inline)) {          // v: step index of the depth
         const lds_f64* tk = ring_row(v) + lc3;
         double c = o.bc;
-        const double Ev = E_of(v, o.E);
+        const double Ev = E_of(v);
         if constexpr (FOLD) { double e_ = 0.0; fast_fold(v, Ev, u_la, c, e_); }
 #pragma unroll
         for (int u = 0; u < NPT; ++u) {
@@ -523,7 +412,7 @@ lsx_sweep_rs_kernel(const SweepParams p)
     double Iu[NR], chi_prev[NR], S_prev[NR], dtau_prev[NR];
 #pragma unroll
     for (int m = 0; m < NR; ++m) { Iu[m] = 0.0; chi_prev[m] = 1.0; S_prev[m] = 0.0; dtau_prev[m] = 1.0; }
-    Ops opA, opB, opC;
+    Ops opA, opB;
     load_ops(kS, opA);
     load_ops(kS + dk, opB);
     if (dir) {
@@ -571,11 +460,7 @@ lsx_sweep_rs_kernel(const SweepParams p)
                         if (p.colmask && LSX_CONST(uint8_t, p.colmask)[col0 + c] == 0) continue;      // a frozen column keeps its slabs
 #pragma unroll
                         for (int q = 0; q < NV; ++q) {
-#ifdef LSX_NT_ST
-                            __builtin_nontemporal_store((double)park[(c * NV + q) * PE + lane], &gbase[((size_t)c * p.nslot_total * 4 + (size_t)q * 2) * Ns + kk]);
-#else
                             gbase[((size_t)c * p.nslot_total * 4 + (size_t)q * 2) * Ns + kk] = park[(c * NV + q) * PE + lane];
-#endif
                         }
                     }
                 }
@@ -620,9 +505,6 @@ lsx_sweep_rs_kernel(const SweepParams p)
                 const int oc = lane / ER, ov = lane - oc * ER;
                 const bool ocol = oc < ncg && (p.colmask ? LSX_CONST(uint8_t, p.colmask)[col0 + (oc < ncg ? oc : 0)] != 0 : true);
                 auto flush_round = [&](const int v0, const int vr) __attribute__((always_inline)) {
-#ifdef LSX_ABL_EPI_NOFLUSH
-                    return;                 // ablation build (wrong results): the fast values are formed and written to the rows, not reduced or stored
-#endif
                     typedef double lds_pair __attribute__((ext_vector_type(2)));
                     __builtin_amdgcn_wave_barrier();
                     const auto* src = (const __attribute__((address_space(3))) lds_pair*)(rows + ov * LSX_WAVE + (oc < NC ? oc : 0) * LW);
@@ -638,16 +520,6 @@ lsx_sweep_rs_kernel(const SweepParams p)
                     __builtin_amdgcn_wave_barrier();
                 };
                 int v0 = 0, vr = 0;
-#ifdef LSX_ABL_EPI_NOMATH
-                // ablation build (wrong results): the rounds of the reduction and their stores without the arithmetic in front of them
-                for (int q = 0; q < nF; ++q) {
-                    rows[vr * LSX_WAVE + lane] = sI; rows[(vr + 1) * LSX_WAVE + lane] = sPsi;
-                    vr += 2;
-                    if (vr == ER) { flush_round(v0, ER); v0 += ER; vr = 0; }
-                }
-                if (vr > 0) flush_round(v0, vr);
-                return;
-#endif
                 for (int q0 = 0; q0 < nF;) {                               // one atom's run of continua at a time
                     int q1 = q0 + 1;
                     while (q1 < nF && !(qi[q1] & 0x80000000u)) ++q1;
@@ -1090,7 +962,7 @@ lsx_sweep_rs_kernel(const SweepParams p)
         const double hdz = ring_row(s)[lcg];                         // the interval behind this ray: row k (down) / k + 1 (up)
         double etaB = cur.be + ring_row(s)[lcg + 1] * cur.jd;
         double chiB = cur.bc;
-        const double Ek = E_of(s, cur.E);
+        const double Ek = E_of(s);
         fast_fold(s, Ek, u_la, chiB, etaB);
         double X[NS], Vjc[NS], Ujc[NS], chic[NS], njUc[NS], njc[NS], w3k[NS];   // lines: X = cB (n_i - g n_j), n_j Uc, wphi; continua: Vji, Uji, chi, n_j
 #pragma unroll
@@ -1115,14 +987,7 @@ lsx_sweep_rs_kernel(const SweepParams p)
         // the next depth's operands are requested HERE, after the ray-independent part has consumed this depth's background,
         // populations and geometry: their registers are free again, so the two operand sets overlap only in the profiles
         // (the first point's neighbour was loaded for the boundary condition)
-        if constexpr (PF2) {
-            // two depths of prefetch: the request goes two steps ahead into the buffer the PREVIOUS step consumed (three operand sets
-            // rotate, nothing is copied); the last-but-one step repeats the end point's request (a valid address, never used), so
-            // every step of a phase issues the same loads and the compiler's vmcnt counts stay exact
-            if constexpr (!LAST) load_ops(s + 2 < Ns ? k + 2 * dk : kS + dk * (Ns - 1), nxt);
-        } else {
-            if constexpr (!LAST && !FIRST) load_ops(k + dk, nxt);
-        }
+        if constexpr (!LAST && !FIRST) load_ops(k + dk, nxt);
         ring_step(s);       // the operand ring moves on by one row (one more load per step, the same in every step)
 
         // ---- the five rays of this wavelength, in three straight-line passes so that the five independent chains interleave
@@ -1341,17 +1206,15 @@ lsx_sweep_rs_kernel(const SweepParams p)
         }
 
         // ---- the wavelength's sums leave: Psibar, Psi* phi, the Gamma integrands (parked for the lane reduction), J
-#ifndef LSX_ABL_NOSTORE
         // lanes without a wavelength of their own shadow a real lane and hold its values: they store the same bits to the same
         // address, so the store needs no lane mask (no branch around it: the compiler counts it when it places its waits -- loads and
         // stores retire in issue order, a wait for the next depth's operands waits for every store before them); the
         // Psibar of a frozen column is read by nobody (the fast-continuum kernels skip frozen columns)
         // (EPI: only the FIRST visitor of a depth stores them -- for the second visitor, which finishes the fast continua's rates itself)
-        if constexpr (!EPI || PH == 0) { if (LK || nF > 0) st_once(psibar, kt, Pacc); }      // (a tile with linked continua has fast continua: no test at all in those instances)
-#endif
+        if constexpr (!EPI || PH == 0) { if (LK || nF > 0) at(psibar, kt) = Pacc; }      // (a tile with linked continua has fast continua: no test at all in those instances)
         if constexpr (LK && (!EPI || PH == 0)) {       // (no lane mask either: shadow lanes repeat their lane's store, a frozen column's sums are read by nobody)
 #pragma unroll
-            for (int u = 0; u < NL; ++u) st_once(ppsum, (unsigned)(u * plane) * 8u + o_pp + (unsigned)(k * LW) * 8u, PP[u]);
+            for (int u = 0; u < NL; ++u) at(ppsum, (unsigned)(u * plane) * 8u + o_pp + (unsigned)(k * LW) * 8u) = PP[u];
         }
         if constexpr (NPT >= 1) {
             // lanes (c, j) -> element c * 12 + j of the value's row (= the lane number); idle lanes park zeros
@@ -1363,11 +1226,7 @@ lsx_sweep_rs_kernel(const SweepParams p)
             }
         }
         if constexpr (PH == 0) {
-#ifdef LSX_ABL_NOSTORE
-            if (valid && Jacc == 1.2345) at(Jnew, kt) = Jacc;
-#else
             at(Jnew, kt) = live_col ? Jacc : cur.jd;                      // first visitor stores its half (frozen: J moves over; no lane mask, see Psibar)
-#endif
         } else if constexpr (PH == 1) {                                   // odd Nspace: both waves are at the same depth
             lds_f64* const xwg = etab + LSX_EXP_TAB + 2 * (NV + 1) * RROW;
             xwg[dir * LSX_WAVE + lane] = Jacc;
@@ -1400,40 +1259,21 @@ lsx_sweep_rs_kernel(const SweepParams p)
                 for (int u = 0; u < NLK; ++u) PPt[u] = pph[u] + ((LK && u < NL) ? PP[u] : 0.0);
                 epi_fast(s, k, Jv, phalf + Pacc, PPt, Ek, X, njUc, w3k);
             }
-#ifdef LSX_ABL_NOSTORE
-            if (valid && Jv == 1.2345) at(Jnew, kt) = Jv;
-#else
-            st_once(Jnew, kt, live_col ? Jv : cur.jd);       // (the total: read again by the NEXT call only)
-#endif
+            at(Jnew, kt) = live_col ? Jv : cur.jd;       // (the total: read again by the NEXT call only)
             if (act) dJ = nanmax(dJ, fabs(1.0 - cur.jd * rcp(Jv)));             // :705
         }
     };
     {
         // the operand buffers swap roles, two steps per loop trip -- where the two-step body fits the register file; the other
         // two-slot tiles take one step per trip and one copy of the operands per step
-#if defined(LSX_RS_SWAP2)
-        constexpr bool SWAP = true;
-#elif defined(LSX_RS_NOSWAP)
-        constexpr bool SWAP = false;
-#else
         constexpr bool SWAP = NPT <= 1 || (!LK && TOPO != 0);      // (two lines with a known relation, no linked continua: 2 spilled registers)
-#endif
         auto one = [&](int s, auto ph) __attribute__((always_inline)) {
-            if constexpr (PF2) {
-                const int r = s % 3;                 // step s reads set s mod 3 and requests depth s + 2 into set (s + 2) mod 3
-                if (r == 0) step(s, ph, opA, opC); else if (r == 1) step(s, ph, opB, opA); else step(s, ph, opC, opB);
-            }
-            else if constexpr (SWAP) { if (s & 1) step(s, ph, opB, opA); else step(s, ph, opA, opB); }
+            if constexpr (SWAP) { if (s & 1) step(s, ph, opB, opA); else step(s, ph, opA, opB); }
             else { step(s, ph, opA, opB); opA = opB; }
         };
         auto run = [&](int s0, int s1, auto ph) __attribute__((always_inline)) {           // steps [s0, s1) of one phase
             int s = s0;
-            if constexpr (PF2) {
-                while (s < s1 && s % 3 != 0) { one(s, ph); ++s; }
-                __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0): no load is pending on any path into the loop
-                for (; s + 2 < s1; s += 3) { step(s, ph, opA, opC); step(s + 1, ph, opB, opA); step(s + 2, ph, opC, opB); }
-                for (; s < s1; ++s) one(s, ph);
-            } else if constexpr (SWAP) {
+            if constexpr (SWAP) {
                 if (s < s1 && (s & 1)) { step(s, ph, opB, opA); ++s; }
                 __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0): no load is pending on any path into the loop
                 for (; s + 1 < s1; s += 2) { step(s, ph, opA, opB); step(s + 1, ph, opB, opA); }
@@ -1449,9 +1289,8 @@ lsx_sweep_rs_kernel(const SweepParams p)
         unsigned long long tk0, tr0, tk1, tr1;
         asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(tk0), "=s"(tr0)::"memory");
 #endif
-        if constexpr (PF2) step(0, std::integral_constant<int, 4>{}, opA, opC);     // ... and requests depth 2 into the third set
-        else step(0, std::integral_constant<int, 4>{}, opA, opB);     // the ray's first point (depth 1 is already requested: its load is skipped there)
-        if constexpr (!SWAP && !PF2) opA = opB;
+        step(0, std::integral_constant<int, 4>{}, opA, opB);     // the ray's first point (depth 1 is already requested: its load is skipped there)
+        if constexpr (!SWAP) opA = opB;
         run(1, nA, std::integral_constant<int, 0>{});
         if (Ns & 1) one(nA, std::integral_constant<int, 1>{});
         run(nA + (Ns & 1), Ns - 1, std::integral_constant<int, 2>{});

@@ -20,7 +20,7 @@ elif [ "$MODE" = rs ]; then     # the ray-serial sweep (lsx_sweep_rs.hip) with t
   /opt/rocm/bin/hipcc $CF $XF -c lsx_sweep_rs.hip -o /tmp/lsxvar/$NAME.o
   g++ -O2 -std=c++17 -fPIC $XD -c lsx_plan.cpp -o /tmp/lsxvar/${NAME}_plan.o
   /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o ../../ab_so/$NAME.so build/lsx_hip.o build/lsx_setup.o /tmp/lsxvar/id_$NAME.o build/lsx_grid.o /tmp/lsxvar/${NAME}_plan.o build/lsx_sweep.o /tmp/lsxvar/$NAME.o build/lsx_sweep_rs_par.o
-elif [ "$MODE" = all ]; then    # every translation unit that sees lsx_plan.h's switches: runtime, both ray-serial units, the plan (e.g. -DLSX_ELANE=0: round 5's operand layout)
+elif [ "$MODE" = all ]; then    # every translation unit that sees lsx_plan.h's switches: runtime, both ray-serial units, the plan (e.g. -DLSX_RS_WPE1=3: the ray-serial instances' register budget)
   /opt/rocm/bin/hipcc $CF $XF -c lsx_hip.hip -o /tmp/lsxvar/${NAME}_hip.o &
   /opt/rocm/bin/hipcc $CF $XF -c lsx_sweep_rs.hip -o /tmp/lsxvar/$NAME.o &
   /opt/rocm/bin/hipcc $CF -DLSX_RS_PARABOLIC_TU $XF -c lsx_sweep_rs.hip -o /tmp/lsxvar/${NAME}_par.o &
