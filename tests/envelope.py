@@ -111,8 +111,13 @@ def first_call_inside(oracle_lib, prob, block, I, J, solver='linear', base=1e-11
 # with tol the single-call bar of the problem, spread the largest relative +-1-ulp spread of the quantity, delta_n = the deviation of
 # the two implementations' populations MEASURED after the preceding statistical equilibrium (asserted below bar_n there; the largest over
 # the atoms).
+# The chain is capped: every delta_n that check_n accepts -- and that then feeds the propagation terms above -- must also be at most
+# C_CHAIN x the largest ORACLE-ONLY population bar of that call over the atoms (K_ENVELOPE spread_n + K_LU u cond + 2 tol, no delta_n):
+# a number the run under test cannot move, so a deviation that grows from iteration to iteration (up to 4 x per iteration would pass
+# the propagation terms alone) is stopped at a fixed multiple of what rounding explains.  CaII (the C5 columns): the cap is about 1e-9.
 K_LU = 3.0
 U_ROUND = 2.0 ** -53
+C_CHAIN = 10.0
 
 
 def lu_condition(prob, Gamma, n_old, n_new):
@@ -149,8 +154,10 @@ class SequenceBars:
     call index >= se_from, and the LU's conditioning at every one of those: the computed bars of the header above.
     make_engine() -> a loaded oracle Engine."""
 
-    def __init__(self, oracle_lib, make_engine, prob, ncalls, se_from, tol=1e-12):
-        """tol: the single-call bar of this problem (1e-12: SURVEY 8d; 3e-11 where a ray crosses an interval next to w2's Taylor switch)"""
+    def __init__(self, oracle_lib, make_engine, prob, ncalls, se_from, tol=1e-12, what=(_capi.LSX_I, _capi.LSX_J, _capi.LSX_GAMMA), what0=()):
+        """tol: the single-call bar of this problem (1e-12: SURVEY 8d; 3e-11 where a ray crosses an interval next to w2's Taylor switch);
+        what: the snapshots kept after every formal solution (J of many columns through many calls is large: leave it out where no J
+        is checked; the populations and the per-column monitors are always kept); what0: kept of the plain run only"""
         self.prob, self.se_from, self.tol = prob, se_from, tol
         self.runs, self.cond = {}, {}
         try:
@@ -160,32 +167,39 @@ class SequenceBars:
                 snaps = []
                 for it in range(ncalls):
                     dJ = e.formal_sol_gamma()
-                    s = {w: e.get(w) for w in (_capi.LSX_I, _capi.LSX_J, _capi.LSX_GAMMA)}
+                    s = {w: e.get(w) for w in what}
                     s['dJ'] = dJ
                     if ulp == 0:
                         s[_capi.LSX_DJ_COL] = e.get(_capi.LSX_DJ_COL)
+                        s.update({w: e.get(w) for w in what0})
                     if se_from is not None and it >= se_from:
                         n_old = e.get(_capi.LSX_N)
+                        gamma = s[_capi.LSX_GAMMA] if _capi.LSX_GAMMA in s else e.get(_capi.LSX_GAMMA)
                         s['dP'] = e.stat_equil()
                         s[_capi.LSX_N] = e.get(_capi.LSX_N)
                         if ulp == 0:
-                            self.cond[it] = lu_condition(prob, s[_capi.LSX_GAMMA], n_old, s[_capi.LSX_N])
+                            s[_capi.LSX_DPOPS_COL] = e.get(_capi.LSX_DPOPS_COL)
+                            self.cond[it] = lu_condition(prob, gamma, n_old, s[_capi.LSX_N])
                     snaps.append(s)
                 e.close()
                 self.runs[ulp] = snaps
         finally:
             oracle_lib.dll.lsx_oracle_set_exp_ulp(0)
 
-    def subset(self, ncol):
-        """the bars of the first `ncol` columns of the ensemble (columns are independent problems: the runs' snapshots are sliced; the
-        LU's condition number stays the larger set's maximum; the scalar monitors dJ / dP are maxima over ALL columns and are dropped)"""
+    def subset(self, cols):
+        """the bars of some columns of the ensemble: the first `cols` (an int) or the columns of a list of indices (columns are
+        independent problems, and a frozen column keeps its bits: the runs' snapshots are sliced, the per-column monitors with them;
+        the LU's condition number stays the larger set's maximum; the scalar monitors dJ / dP are maxima over ALL columns and are
+        dropped)"""
         import copy
+        sel = slice(0, cols) if isinstance(cols, (int, np.integer)) else np.asarray(cols, dtype=np.int64)
         b = copy.copy(self)
-        b.runs = {u: [{k: (v[:ncol] if isinstance(v, np.ndarray) else None) for k, v in s.items()} for s in snaps] for u, snaps in self.runs.items()}
+        b.runs = {u: [{k: (v[sel] if isinstance(v, np.ndarray) else None) for k, v in s.items()} for s in snaps] for u, snaps in self.runs.items()}
         return b
 
     def oracle(self, call, what):
         return self.runs[0][call][what]
+
 
     def _rel(self, a, b):
         a, b = np.asarray(a), np.asarray(b)
@@ -202,6 +216,11 @@ class SequenceBars:
             off += nl
         return bars
 
+    def chain_cap(self, call):
+        """the largest delta_n a propagation term may be fed with after the statistical equilibrium behind `call`: C_CHAIN x the
+        largest oracle-only population bar of that call over the atoms (n_bar without its delta_n term)"""
+        return C_CHAIN * max(self.n_bar(call, 0.0))
+
     def n_dev(self, n, ref, call=None):
         """measured relative deviation per atom"""
         n, ref = np.asarray(n), np.asarray(ref)
@@ -212,10 +231,16 @@ class SequenceBars:
             off += nl
         return out
 
-    def check_n(self, n, ref, call, who='', delta_n_prev=0.0):
-        dev, bar = self.n_dev(n, ref), self.n_bar(call, delta_n_prev)
+    def check_n(self, n, ref, call, who='', delta_n_prev=0.0, quiet=False):
+        """the populations after the statistical equilibrium behind `call` against their computed bars and the chain's cap.
+        -> the largest deviation over the atoms (what the next propagation terms are fed with)"""
+        dev, bar, cap = self.n_dev(n, ref), self.n_bar(call, delta_n_prev), self.chain_cap(call)
+        if not quiet:
+            print('check_n call %d%s: delta_n %.2e, cap %.2e, delta_n / cap %.3f' % (call + 1, who, max(dev), cap, max(dev) / cap))
         assert all(d <= b for d, b in zip(dev, bar)), ('populations after the statistical equilibrium behind call %d%s: deviation per atom %s '
                                                        'above the computed bars %s (u cond = %s)' % (call + 1, who, dev, bar, [U_ROUND * c for c in self.cond[call]]))
+        assert max(dev) <= cap, ('populations after the statistical equilibrium behind call %d%s: deviation %.3e above the chain cap %.3e '
+                                 '(C_CHAIN = %g x the largest oracle-only bar)' % (call + 1, who, max(dev), cap, C_CHAIN))
         return max(dev)
 
     def _spread(self, call, what, floor=1e-300):
@@ -250,3 +275,23 @@ class SequenceBars:
     def gamma_bar(self, call, delta_n, gamma_err):
         eo, ed = gamma_err(self.runs[1][call][_capi.LSX_GAMMA], self.runs[-1][call][_capi.LSX_GAMMA], self.prob)
         return 10.0 * self.tol + K_ENVELOPE * eo + 4.0 * delta_n, self.tol + K_ENVELOPE * ed + 4.0 * delta_n
+
+
+def monitor_excess(m, m_ref, x, x_ref, x_prev, x_ref_prev, rel=1e-6):
+    """per-column monitors (LSX_DJ_COL: the largest relative change of J over a call, LSX_DPOPS_COL: of the populations) against the
+    oracle's.  A monitor is a relative change: where the two implementations' x (J or n, now and one call before) differ by eps
+    relative, it moves by up to 2 eps (1 + m) ABSOLUTE -- a small change of x (J before the first statistical equilibrium, a
+    converging column) is known only that well.  Bar per column: rel |m_ref| + 2 (1 + |m_ref|) eps, eps the largest relative deviation
+    of x of that column at the two calls (x_prev = None: identical inputs one call before).  -> largest deviation / bar per column"""
+    def dev(a, b):
+        a, b = np.asarray(a), np.asarray(b)
+        r = np.abs(a - b) / np.maximum(np.abs(b), 1e-300)
+        r = np.where(np.abs(b) > 0, r, np.where(a == b, 0.0, np.inf))
+        return r.reshape(r.shape[0], -1).max(axis=1)
+    eps = dev(x, x_ref)
+    if x_prev is not None:
+        eps = np.maximum(eps, dev(x_prev, x_ref_prev))
+    m, m_ref = np.asarray(m), np.asarray(m_ref)
+    bar = rel * np.abs(m_ref) + 2.0 * (1.0 + np.abs(m_ref)) * eps
+    d = np.abs(m - m_ref)
+    return np.where(bar > 0, d / np.maximum(bar, 1e-300), np.where(d > 0, np.inf, 0.0))

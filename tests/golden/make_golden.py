@@ -12,7 +12,7 @@ under /root/reference is touched:
     arrays (numpy<1.25 semantics; only used for list membership in setup).
 (np.bool, used at rh_method.py:124, exists again in numpy 2.x.)
 
-Usage:  python tests/golden/make_golden.py [units] [falc_ca] [falc_cah] [falc_ca_vlos] [falc_c] [falc_fe] [falc_mg] [falc_all] [rf] [rf_inputs] [setup] [live_ref] [all]
+Usage:  python tests/golden/make_golden.py [units] [falc_ca] [falc_cah] [falc_ca_vlos] [falc_c] [falc_fe] [falc_mg] [falc_all] [rf] [rf_inputs] [rf_outputs] [setup] [live_ref] [all]
 """
 import os
 import sys
@@ -408,6 +408,83 @@ def gen_rf_inputs(out_name='rf_ca_inputs.npz'):
     save(out_name, out)
 
 
+def _delta_encode(dp, dbase, k):
+    """gen_rf_inputs' delta encoding of one perturbed run: {key: v[..., k]} for every input array that differs from the base
+    column's, asserting that it differs at depth k only"""
+    out = {}
+    for key, v in dp.items():
+        b = dbase[key]
+        if v.dtype.kind in 'USib':
+            assert np.array_equal(v, b), key
+            continue
+        if key.endswith('_n0') or np.array_equal(v, b):
+            continue
+        if key == 'height':
+            assert np.array_equal(np.diff(v), np.diff(b)), 'height diff changed'
+            continue
+        diff = (v != b)
+        where_k = np.zeros_like(diff)
+        where_k[..., k] = True
+        assert not np.any(diff & ~where_k), 'non-local change in %s' % key
+        out[key] = v[..., k].copy()
+    return out
+
+
+_RF_WORKER = {}
+
+
+def _rf_worker_init(dbase, base_n, inputs_path):
+    _RF_WORKER.update(dbase=dbase, base_n=base_n, inputs=dict(np.load(inputs_path)))
+
+
+def _rf_run(job):
+    """one perturbed run of gen_rf_outputs (in a worker process): -> (pre, {result key: array})"""
+    k, sgn, tag = job
+    w = _RF_WORKER
+    pre = 'k%d%s_' % (k, tag)
+    ctx = build_ctx(['Ca'], temp_pert=(k, sgn * 25.0), start_pops={'Ca': w['base_n']})
+    # the inputs of this run are, bit for bit, the ones rf_ca_inputs.npz holds for it
+    mine = _delta_encode(dump_inputs(ctx), w['dbase'], k)
+    theirs = {key[len(pre):]: v for key, v in w['inputs'].items() if key.startswith(pre)}
+    assert set(mine) == set(theirs), (pre, sorted(set(mine) ^ set(theirs)))
+    for key, v in mine.items():
+        assert np.array_equal(v, theirs[key]), pre + key
+    t = {}
+    n = run_mali(ctx, t, snap_iters=())
+    return pre, {'I': ctx.I[:, -1:].copy(), 'n': ctx.activeAtoms[0].n.copy(), 'niter': np.int32(n),
+                 'traj_dJ': t['traj_dJ'], 'traj_dPops': t['traj_dPops']}
+
+
+def gen_rf_outputs(out_name='rf_ca_outputs.npz', workers=16):
+    """the reference's converged OUTPUTS of all 2 x Nspace perturbed runs of response_fn.py:23-57 (the inputs are
+    rf_ca_inputs.npz's; every run's delta-encoded inputs are asserted equal to that file's bit for bit), warm started like
+    gen_rf from the reference's own converged base populations.  Per run: I at mu index -1 only (what the response function
+    uses; all rays would put the file over the size limit of a committed file), n, the iteration count and the dJ / dPops
+    trajectories; base_I (all rays), base_n, base_niter.  A pool of at most `workers` processes (about 10 s per run).
+    Even so the plain arrays compress to 1.15 MB: every run's I and n are stored as their float64 bit patterns XOR those of the
+    base column's (base_I[:, -1:], base_n; uint64, lossless), whose leading bits they share -- 0.93 MB.  Decode with
+    (x ^ base.view(np.uint64)).view(np.float64)."""
+    import multiprocessing as mp
+    base = build_ctx(['Ca'])
+    dbase = dump_inputs(base)
+    tmp = {}
+    run_mali(base, tmp, snap_iters=(), log='rf_base')
+    base_n = base.eqPops['Ca'].n.copy()
+    out = {'base_I': base.I.copy(), 'base_n': base.activeAtoms[0].n.copy(), 'base_niter': tmp['n_iter']}
+    Ns = base.atmos.Nspace
+    jobs = [(k, sgn, tag) for k in range(Ns) for sgn, tag in ((+1, 'p'), (-1, 'm'))]
+    t0 = time.time()
+    nproc = max(1, min(workers, len(os.sched_getaffinity(0))))
+    with mp.get_context('spawn').Pool(nproc, _rf_worker_init, (dbase, base_n, os.path.join(HERE, 'rf_ca_inputs.npz'))) as pool:
+        for q, (pre, res) in enumerate(pool.imap(_rf_run, jobs)):
+            res['I'] = res['I'].view(np.uint64) ^ out['base_I'][:, -1:].copy().view(np.uint64)
+            res['n'] = res['n'].view(np.uint64) ^ out['base_n'].view(np.uint64)
+            for key, v in res.items():
+                out[pre + key] = v
+            print('rf outputs: %s%d iterations  (%d / %d, %.0f s)' % (pre, res['niter'], q + 1, len(jobs), time.time() - t0), flush=True)
+    save(out_name, out)
+
+
 def _atom_data(model, d, pre, fresh):
     """numeric content of one AtomicModel (rh_atoms.py data, atomic_model.py derived constants) as flat arrays.
     `fresh` is an identical model on which compute_wavelength_grid has NOT run: its transitions still carry the local
@@ -588,6 +665,6 @@ if __name__ == '__main__':
         t0 = time.time()
         {'units': gen_units, 'falc_ca': gen_falc_ca, 'falc_cah': gen_falc_cah,
          'falc_ca_vlos': gen_falc_ca_vlos, 'rf': gen_rf, 'falc_c': lambda: gen_falc_multilevel('c'),
-         'falc_fe': lambda: gen_falc_multilevel('fe'), 'falc_mg': lambda: gen_falc_multilevel('mg'), 'falc_all': gen_falc_all, 'rf_inputs': gen_rf_inputs, 'setup': gen_setup,
+         'falc_fe': lambda: gen_falc_multilevel('fe'), 'falc_mg': lambda: gen_falc_multilevel('mg'), 'falc_all': gen_falc_all, 'rf_inputs': gen_rf_inputs, 'rf_outputs': gen_rf_outputs, 'setup': gen_setup,
          'live_ref': gen_live_ref}[w]()
         print('%s done in %.1fs' % (w, time.time() - t0), flush=True)

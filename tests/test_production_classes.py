@@ -43,6 +43,13 @@ def class_table(lib, eng):
     return table, fused
 
 
+def _monitor_cols(what, m, m_ref, call, *x):
+    """the per-column monitor `what` (LSX_DJ_COL / LSX_DPOPS_COL) of the HIP engine against the oracle's after `call`, column by column:
+    rel 1e-6, or what the deviation of J / n at this call and the one before explains (envelope.monitor_excess)"""
+    r = envelope.monitor_excess(m, m_ref, *x)
+    assert np.all(r <= 1.0), ('call %d: per-column monitor %d of columns %s: %s x the bar' % (call + 1, what, np.flatnonzero(~(r <= 1.0)), r[~(r <= 1.0)]))
+
+
 _BARS = {}      # (fixture, columns, seed, iterations) -> envelope.SequenceBars: the two mappings of a case share the oracle's three runs
 
 
@@ -90,14 +97,23 @@ def _run_pair(hip_lib, oracle_lib, name, ncol, seed, tol, expect_classes, iters=
     assert np.allclose(hip.get(_capi.LSX_DJ_COL), ora(0, _capi.LSX_DJ_COL), rtol=1e-9)
     # ---- `iters` (8) MALI iterations (test.py:20-29: the first three update J only)
     dn = dn_in = 0.0
+    J_prev, n_prev = hip.get(_capi.LSX_J), None
     for it in range(2, iters + 1):
         dJ = hip.formal_sol_gamma()
         if nbar == ncol:
             assert dJ == pytest.approx(full.oracle(it - 1, 'dJ'), rel=1e-6)
+        J = hip.get(_capi.LSX_J)                                # column by column, the subset cases too
+        _monitor_cols(_capi.LSX_DJ_COL, hip.get(_capi.LSX_DJ_COL), ora(it - 1, _capi.LSX_DJ_COL), it - 1,
+                      J, ora(it - 1, _capi.LSX_J), J_prev, ora(it - 2, _capi.LSX_J))
+        J_prev = J
         if it > 3:
             dP = hip.stat_equil()
             if nbar == ncol:
                 assert dP == pytest.approx(full.oracle(it - 1, 'dP'), rel=1e-6)
+            n = hip.get(_capi.LSX_N)
+            _monitor_cols(_capi.LSX_DPOPS_COL, hip.get(_capi.LSX_DPOPS_COL), ora(it - 1, _capi.LSX_DPOPS_COL), it - 1,
+                          n, ora(it - 1, _capi.LSX_N), n_prev, None if n_prev is None else ora(it - 2, _capi.LSX_N))
+            n_prev = n
             dn_in = dn                                          # what the populations differed by going into this iteration's formal solution
             dn = bars.check_n(hip.get(_capi.LSX_N), ora(it - 1, _capi.LSX_N), it - 1, ' (HIP vs oracle, iteration %d)' % it, dn_in)
     bI, eI = bars.I_bar(iters - 1, dn_in), relerr(hip.get(_capi.LSX_I), ora(iters - 1, _capi.LSX_I))

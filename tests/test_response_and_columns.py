@@ -151,6 +151,12 @@ def _rf_all_depths(lib):
         assert np.allclose(out['rf'][:, k], ref, rtol=0, atol=2e-6 * np.max(np.abs(ref)))
         assert out['n_iter'][2 * k] == int(rf['k%dp_niter' % k]) and out['n_iter'][2 * k + 1] == int(rf['k%dm_niter' % k])
     assert np.all(np.isfinite(out['rf']))
+    # every depth: the iteration counts of the reference's own 164 runs (rf_ca_outputs.npz; the bars on I, n and rf at every depth:
+    # tests/test_response_every_depth.py)
+    from test_response_every_depth import load_rf_outputs
+    outs = load_rf_outputs()
+    want = np.array([int(outs['k%d%s_niter' % (k, tag)]) for k in range(82) for tag in ('p', 'm')])
+    assert np.array_equal(out['n_iter'], want), np.flatnonzero(out['n_iter'] != want)
 
 
 def test_response_function_all_depths_oracle(oracle_lib):
