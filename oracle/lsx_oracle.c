@@ -321,9 +321,14 @@ int lsx_set_atomic_data(lsx_ctx* c, const lsx_atomic_data* d)
         int nl = 0;
         for (int t = 0; t < c->Ntrans; ++t) nl += c->trans[t].is_line && c->trans[t].atom == a;
         if (m->Nlevel != c->Nlevel[a] || m->Nline != nl || !(m->weight > 0.0)) return fail(LSX_EINVAL, "lsx_set_atomic_data: atom does not match the context");
-        for (int q = 0; q < m->Ncollision; ++q)
-            if (m->collisions[q].nT < 2 || m->collisions[q].nT == 3 || m->collisions[q].i >= m->collisions[q].j)
+        for (int q = 0; q < m->Ncollision; ++q) {
+            const lsx_collision* K = &m->collisions[q];
+            if (K->nT < 2 || K->nT == 3 || K->i < 0 || K->j >= m->Nlevel || K->i >= K->j || !K->temperature || !K->rates)
                 return fail(LSX_EINVAL, "lsx_set_atomic_data: inconsistent collision");
+            /* the reference's interp1d sorts its table; a descending or repeated temperature is refused, as the HIP library does */
+            for (int e = 1; e < K->nT; ++e)
+                if (!(K->temperature[e] > K->temperature[e - 1])) return fail(LSX_EINVAL, "lsx_set_atomic_data: temperatures must ascend");
+        }
     }
     free_atomic_data(c);
     if (c->Natoms < 1) return fail(LSX_EINVAL, "lsx_set_atomic_data: the context has no atoms");
@@ -400,8 +405,8 @@ static void spline_moments(int n, const double* x, const double* y, double* M)
 {
     for (int i = 0; i < n; ++i) M[i] = 0.0;
     if (n < 4) return;
-    double A[64 * 64], b[64];
-    memset(A, 0, sizeof(double) * (size_t)n * n);
+    double* A = (double*)calloc((size_t)n * n + n, sizeof(double));   /* n x n system, then b: a table of any length */
+    double* b = A + (size_t)n * n;
 #define H(i) (x[(i) + 1] - x[(i)])
     A[0] = H(1); A[1] = -(H(0) + H(1)); A[2] = H(0); b[0] = 0.0;
     A[(n - 1) * n + n - 3] = H(n - 2); A[(n - 1) * n + n - 2] = -(H(n - 3) + H(n - 2)); A[(n - 1) * n + n - 1] = H(n - 3); b[n - 1] = 0.0;
@@ -421,6 +426,7 @@ static void spline_moments(int n, const double* x, const double* y, double* M)
         }
     }
     for (int r = n - 1; r >= 0; --r) { double sacc = b[r]; for (int q = r + 1; q < n; ++q) sacc -= A[r * n + q] * M[q]; M[r] = sacc / A[r * n + r]; }
+    free(A);
 }
 static double spline_eval(int n, const double* x, const double* y, const double* M, double t)
 {
@@ -505,7 +511,7 @@ int lsx_set_atmosphere(lsx_ctx* c, int32_t col0, int32_t ncol, const lsx_atmosph
             for (size_t e = 0; e < (size_t)Nl * Nl * Ns; ++e) Cm[e] = 0.0;
             for (int q = 0; q < m->Ncollision; ++q) {
                 const lsx_collision* K = &m->collisions[q];
-                double M[64];
+                double* M = (double*)malloc(sizeof(double) * (size_t)K->nT);
                 spline_moments(K->nT, K->temperature, K->rates, M);
                 const lsx_level *jL = &m->levels[K->j], *iL = &m->levels[K->i];
                 for (int k = 0; k < Ns; ++k) {
@@ -530,6 +536,7 @@ int lsx_set_atmosphere(lsx_ctx* c, int32_t col0, int32_t ncol, const lsx_atmosph
                         *Cji += Cdown * nsj / nsi;
                     }
                 }
+                free(M);
             }
             for (size_t e = 0; e < (size_t)Nl * Nl * Ns; ++e) if (Cm[e] < 0.0) Cm[e] = 0.0;
         }

@@ -155,18 +155,26 @@ def context_native_setup_chain(lib, name='falc_cah.npz'):
     """models that carry their atomic data: Context hands them to lsx_set_atomic_data and the library derives vBroad,
     aDamp, the profiles and the collisional rates from the atmosphere (lsx_set_atmosphere); everything the reference's
     constructor would have computed is read back and compared with what the reference did compute (1e-13: the device
-    evaluates the same formulas with its own exp / log / sqrt / Faddeeva; phi on a ray-dependent profile 1e-12)"""
+    evaluates the same formulas with its own exp / log / sqrt / Faddeeva; phi on a ray-dependent profile 1e-12; the rates
+    entry by entry inside the bars of tests/setup_cases.py).  The models' data: tests/golden/setup_atoms.npz, all five atoms"""
+    from lightspinner_amd import atomdata
+    from setup_cases import Ledger, rates_and_bars, check_rates
     d = dict(np.load(golden(name)))
-    s = dict(np.load(golden('setup_falc.npz')))
+    s = dict(np.load(golden('setup_atoms.npz')))
     atmos, spect, eq, bg = build_data_fakes(d, s)
     ctx = Context(atmos, spect, eq, bg, lib=lib)
     assert ctx.setup == 'native'
+    names = [str(x) for x in s['atom_names']]
+    data = atomdata.from_fixture(s)
+    led = Ledger('%s %s native set-up' % (getattr(lib, 'backend', 'hip'), name))
     kr = 0
     for a, atom in enumerate(ctx.activeAtoms):
         assert relerr(atom.vBroad, d['a%d_vBroad' % a]) < 1e-14
         C, Cref = atom.C, d['a%d_C' % a]
         assert C.shape == Cref.shape
         assert np.max(np.abs(C - Cref)) <= 1e-12 * np.max(np.abs(Cref))
+        _, bar = rates_and_bars(data.atoms[names.index(atom.atomicModel.name)], d['temperature'], d['ne'], d['a%d_nStar' % a])
+        check_rates(led, 'C', C, Cref, bar)
         for t in atom.trans:
             if t.isLine:
                 assert relerr(t.aDamp, d['t%d_aDamp' % kr]) < 1e-13
@@ -191,8 +199,10 @@ def context_native_setup_chain(lib, name='falc_cah.npz'):
     if 'se4_dPops' in d:
         assert dP == pytest.approx(float(d['se4_dPops']), rel=1e-6)
     J = ctx.J.copy()
+    C0 = ctx.activeAtoms[0].C.copy()
     ctx.update_collisions()                              # re-derivation leaves the state where it was
-    assert np.max(np.abs(ctx.activeAtoms[0].C - d['a0_C'])) <= 1e-12 * np.max(np.abs(d['a0_C']))
+    assert np.array_equal(ctx.activeAtoms[0].C, C0)
+    led.report()
     assert np.array_equal(ctx._engine.get(1)[0], J)   # LSX_J
     ctx.close()
 

@@ -12,7 +12,7 @@ under /root/reference is touched:
     arrays (numpy<1.25 semantics; only used for list membership in setup).
 (np.bool, used at rh_method.py:124, exists again in numpy 2.x.)
 
-Usage:  python tests/golden/make_golden.py [units] [falc_ca] [falc_cah] [falc_ca_vlos] [falc_c] [falc_fe] [falc_mg] [falc_all] [rf] [rf_inputs] [rf_outputs] [setup] [live_ref] [all]
+Usage:  python tests/golden/make_golden.py [units] [falc_ca] [falc_cah] [falc_ca_vlos] [falc_c] [falc_fe] [falc_mg] [falc_all] [rf] [rf_inputs] [rf_outputs] [setup] [live_ref] [setup_atoms] [all]
 """
 import os
 import sys
@@ -485,12 +485,11 @@ def gen_rf_outputs(out_name='rf_ca_outputs.npz', workers=16):
     save(out_name, out)
 
 
-def _atom_data(model, d, pre, fresh):
-    """numeric content of one AtomicModel (rh_atoms.py data, atomic_model.py derived constants) as flat arrays.
-    `fresh` is an identical model on which compute_wavelength_grid has NOT run: its transitions still carry the local
-    wavelength grids the merge starts from (atomic_model.py:347-380, 585-597, 645-660)."""
+def _atom_core(model, d, pre):
+    """what the library's set-up chain reads of one AtomicModel (lightspinner_amd/atomdata.py from_fixture,
+    tests/helpers.py build_data_fakes): weight, abundance, levels, each line's damping data, the collision tables"""
     import collisional_rates as cr
-    from atomic_model import VdwUnsold, ExplicitContinuum, HydrogenicContinuum
+    from atomic_model import VdwUnsold
     tab = model.atomicTable
     d[pre + 'weight'] = np.float64(tab[model.name].weight)
     d[pre + 'abundance'] = np.float64(tab[model.name].abundance)
@@ -500,11 +499,39 @@ def _atom_data(model, d, pre, fresh):
     L = model.lines
     d[pre + 'line_i'] = np.array([l.i for l in L], dtype=np.int32)
     d[pre + 'line_j'] = np.array([l.j for l in L], dtype=np.int32)
+    for key in ('gRad', 'stark'):
+        d[pre + 'line_' + key] = np.array([getattr(l, key) for l in L], dtype=np.float64)
+    d[pre + 'line_vdw_unsold'] = np.array([1 if isinstance(l.vdw, VdwUnsold) else 0 for l in L], dtype=np.int32)
+    d[pre + 'line_vdw_vals'] = np.array([list(l.vdw.vals)[:2] for l in L], dtype=np.float64).reshape(len(L), 2)
+    kinds = {cr.Omega: 0, cr.CI: 1, cr.CE: 2}
+    K = model.collisions
+    d[pre + 'col_kind'] = np.array([kinds[type(c)] for c in K], dtype=np.int32)
+    d[pre + 'col_i'] = np.array([c.i for c in K], dtype=np.int32)
+    d[pre + 'col_j'] = np.array([c.j for c in K], dtype=np.int32)
+    nt = max(len(c.temperature) for c in K)
+    d[pre + 'col_nT'] = np.array([len(c.temperature) for c in K], dtype=np.int32)
+    T = np.zeros((len(K), nt)); R = np.zeros((len(K), nt))
+    for q, c in enumerate(K):
+        T[q, :len(c.temperature)] = c.temperature
+        R[q, :len(c.rates)] = c.rates
+    d[pre + 'col_T'] = T
+    d[pre + 'col_rates'] = R
+
+
+def _atom_data(model, d, pre, fresh):
+    """numeric content of one AtomicModel (rh_atoms.py data, atomic_model.py derived constants) as flat arrays.
+    `fresh` is an identical model on which compute_wavelength_grid has NOT run: its transitions still carry the local
+    wavelength grids the merge starts from (atomic_model.py:347-380, 585-597, 645-660)."""
+    from atomic_model import HydrogenicContinuum
+    core = {}
+    _atom_core(model, core, pre)
+    for key in ('weight', 'abundance', 'lev_E_SI', 'lev_g', 'lev_stage', 'line_i', 'line_j'):     # (the file's key order)
+        d[pre + key] = core[pre + key]
+    L = model.lines
     for key in ('f', 'gRad', 'stark', 'lambda0', 'Aji', 'Bji', 'Bij', 'qCore', 'qWing'):
         d[pre + 'line_' + key] = np.array([getattr(l, key) for l in L], dtype=np.float64)
     d[pre + 'line_NlambdaGen'] = np.array([l.NlambdaGen for l in L], dtype=np.int32)
-    d[pre + 'line_vdw_unsold'] = np.array([1 if isinstance(l.vdw, VdwUnsold) else 0 for l in L], dtype=np.int32)
-    d[pre + 'line_vdw_vals'] = np.array([list(l.vdw.vals)[:2] for l in L], dtype=np.float64).reshape(len(L), 2)
+    d[pre + 'line_vdw_unsold'], d[pre + 'line_vdw_vals'] = core[pre + 'line_vdw_unsold'], core[pre + 'line_vdw_vals']
     d[pre + 'line_vdw_cross'] = np.array([getattr(l.vdw, 'cross', 0.0) for l in L], dtype=np.float64)
     for q, l in enumerate(fresh.lines):
         d[pre + 'line%d_grid0' % q] = np.array(l.wavelength)
@@ -521,19 +548,8 @@ def _atom_data(model, d, pre, fresh):
     for q, c in enumerate(Cn):
         d[pre + 'cont%d_alpha' % q] = np.array(c.alpha)             # on the merged grid (compute_alpha)
         d[pre + 'cont%d_wavelength' % q] = np.array(c.wavelength)
-    kinds = {cr.Omega: 0, cr.CI: 1, cr.CE: 2}
-    K = model.collisions
-    d[pre + 'col_kind'] = np.array([kinds[type(c)] for c in K], dtype=np.int32)
-    d[pre + 'col_i'] = np.array([c.i for c in K], dtype=np.int32)
-    d[pre + 'col_j'] = np.array([c.j for c in K], dtype=np.int32)
-    nt = max(len(c.temperature) for c in K)
-    d[pre + 'col_nT'] = np.array([len(c.temperature) for c in K], dtype=np.int32)
-    T = np.zeros((len(K), nt)); R = np.zeros((len(K), nt))
-    for q, c in enumerate(K):
-        T[q, :len(c.temperature)] = c.temperature
-        R[q, :len(c.rates)] = c.rates
-    d[pre + 'col_T'] = T
-    d[pre + 'col_rates'] = R
+    for key in ('col_kind', 'col_i', 'col_j', 'col_nT', 'col_T', 'col_rates'):
+        d[pre + key] = core[pre + key]
 
 
 def gen_setup():
@@ -608,6 +624,101 @@ def gen_setup():
     save('setup_falc.npz', d)
 
 
+SETUP_ATOMS = (('H', H_6_atom), ('C', C_atom), ('MG', MgII_atom), ('CA', CaII_atom), ('FE', Fe_simple_atom))   # falc_all's order
+
+
+def edge_atmosphere(knots, Ns=82, seed=20261016):
+    """temperature, ne, vturb of the `edge` column: below 1000 K, 1000-3000 K, every knot of every collision table exactly,
+    a few knots x (1 -+ 1e-12) and one ulp either side, values between the knots, above 30 000 K and up to 1e6 K; ne log-spaced
+    over 1e12 ... 1e23 m^-3 and vturb over 0 ... 3e4 m/s, both shuffled against the temperatures"""
+    rng = np.random.default_rng(seed)
+    k = np.array(sorted(knots), dtype=np.float64)
+    T = [400.0, 600.0, 800.0, 999.9, 1200.0, 1700.0, 2200.0, 2700.0, 2999.0]
+    T += list(k)
+    for x in (k[0], k[1], k[4], k[7], k[-1]):
+        T += [x * (1.0 - 1e-12), x * (1.0 + 1e-12)]
+    for x in (k[1], k[-1]):
+        T += [np.nextafter(x, 0.0), np.nextafter(x, np.inf)]
+    for lo, hi in zip(k[:-1], k[1:]):
+        T += list(lo + (hi - lo) * np.array([0.13, 0.5, 0.87]))
+    T += [1.2e5, 1.5e5, 2e5, 3e5, 5e5, 7e5, 1e6]
+    T += list(np.exp(rng.uniform(np.log(400.0), np.log(1e6), Ns - len(T))))
+    T = np.array(T)
+    assert T.shape == (Ns,)
+    ne = rng.permutation(np.logspace(12.0, 23.0, Ns))
+    vturb = rng.permutation(np.linspace(0.0, 3e4, Ns))
+    return T, ne, vturb
+
+
+def _setup_chain(models, atmos):
+    """the reference's set-up chain at one atmosphere, called method by method (at the edge temperatures neither
+    Atmosphere.convert_scales nor Background can be built): compute_eq_pops (atomic_set.py:361-375: LTE with Debye
+    lowering), v_broad (atomic_model.py:66-69), each line's damping (:491-502) with H's ground-level population, each
+    collision's compute_rates and the clamp of compute_collisions (rh_method.py:474-487).  models in falc_all's order"""
+    eqPops = RadiativeSet(models).compute_eq_pops(atmos)
+    hGround = np.array(eqPops['H'].n[0])
+    out = {'hGround': hGround}
+    for a, m in enumerate(models):
+        st = eqPops[m.name]
+        vB = np.array(m.v_broad(atmos))
+        Nl = len(m.levels)
+        C = np.zeros((Nl, Nl, atmos.Nspace))
+        for col in m.collisions:
+            col.compute_rates(atmos, st.nStar, C)
+        C[C < 0.0] = 0.0
+        out['a%d_vBroad' % a] = vB
+        out['a%d_nStar' % a] = np.array(st.nStar)
+        out['a%d_nTotal' % a] = np.array(st.nTotal)
+        out['a%d_C' % a] = C
+        out['a%d_aDamp' % a] = np.array([l.damping(atmos, vB, hGround)[0] for l in m.lines])   # model line order
+    return out
+
+
+def gen_setup_atoms():
+    """Atomic data of all five of the reference's model atoms (the keys lightspinner_amd/atomdata.py from_fixture and
+    tests/helpers.py build_data_fakes read) and the reference's set-up outputs for the 82-depth `edge` column
+    (edge_atmosphere: FALC's nHTot, temperatures from 400 K to 1e6 K).  The same code run at FALC must reproduce
+    falc_all.npz's vBroad, nStar, C and aDamp bit for bit; FALC's outputs are not stored a second time."""
+    ref = dict(np.load(os.path.join(HERE, 'falc_all.npz')))
+    models = [ctor() for _, ctor in SETUP_ATOMS]
+    RadiativeSet(models)                                         # gives every model its atomic table
+    assert [m.name for m in models] == [str(x) for x in ref['atom_names']]
+    d = {'atom_names': np.array([m.name for m in models])}
+    for a, m in enumerate(models):
+        _atom_core(m, d, 'm%d_' % a)
+    tab = models[0].atomicTable
+    d['weight_H'], d['weight_He'] = np.float64(tab['H'].weight), np.float64(tab['He'].weight)
+    d['abundance_He'] = np.float64(tab['He'].abundance)
+
+    def falc():
+        ac = Falc82()
+        ac.quadrature(5)
+        atmos = ac.convert_scales()
+        atmos.nondimensionalise()
+        return atmos
+    # FALC: bit for bit what falc_all.npz holds (its Context made the same calls)
+    atmos = falc()
+    assert np.array_equal(np.asarray(atmos.temperature), ref['temperature']) and np.array_equal(np.asarray(atmos.ne), ref['ne'])
+    out = _setup_chain(models, atmos)
+    assert np.array_equal(out['hGround'], ref['hGround'])
+    for a, m in enumerate(models):
+        for key in ('vBroad', 'nStar', 'nTotal', 'C'):
+            assert np.array_equal(out['a%d_%s' % (a, key)], ref['a%d_%s' % (a, key)]), (m.name, key)
+        lines = [kr for kr in range(ref['t_atom'].shape[0]) if ref['t_atom'][kr] == a and ref['t_isline'][kr]]
+        assert [(int(ref['t_i'][kr]), int(ref['t_j'][kr])) for kr in lines] == [(l.i, l.j) for l in m.lines], m.name
+        for q, kr in enumerate(lines):
+            assert np.array_equal(out['a%d_aDamp' % a][q], ref['t%d_aDamp' % kr]), (m.name, kr)
+    knots = {float(x) for m in models for c in m.collisions for x in c.temperature}
+    T, ne, vturb = edge_atmosphere(knots)
+    atmos = falc()
+    atmos.temperature, atmos.ne, atmos.vturb = T, ne, vturb
+    out = _setup_chain(models, atmos)
+    for key in ('temperature', 'ne', 'vturb', 'nHTot'):
+        d['edge_' + key] = np.array(getattr(atmos, key), dtype=np.float64)
+    for key, v in out.items():
+        d['edge_' + key] = v
+    save('setup_atoms.npz', d)
+
 def gen_live_ref(n_iter=6):
     """What tests/test_reference_live.py compares with: the reference's FALC CaII Context (test.py's set-up) through six MALI
     iterations, and the merged wavelength grid of RadiativeSet([CaII, H_6]) with Ca and H active.  Everything falc_ca.npz and
@@ -666,5 +777,5 @@ if __name__ == '__main__':
         {'units': gen_units, 'falc_ca': gen_falc_ca, 'falc_cah': gen_falc_cah,
          'falc_ca_vlos': gen_falc_ca_vlos, 'rf': gen_rf, 'falc_c': lambda: gen_falc_multilevel('c'),
          'falc_fe': lambda: gen_falc_multilevel('fe'), 'falc_mg': lambda: gen_falc_multilevel('mg'), 'falc_all': gen_falc_all, 'rf_inputs': gen_rf_inputs, 'rf_outputs': gen_rf_outputs, 'setup': gen_setup,
-         'live_ref': gen_live_ref}[w]()
+         'live_ref': gen_live_ref, 'setup_atoms': gen_setup_atoms}[w]()
         print('%s done in %.1fs' % (w, time.time() - t0), flush=True)

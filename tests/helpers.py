@@ -179,7 +179,7 @@ class DataAtom:
 
 
 def build_data_fakes(d, s, start_pops=None):
-    """like build_fakes, with models that hold atomic data (d: a problem fixture, s: setup_falc.npz)"""
+    """like build_fakes, with models that hold atomic data (d: a problem fixture, s: setup_atoms.npz or setup_falc.npz)"""
     names = [str(x) for x in s['atom_names']]
     table = {n: _Element(s['m%d_weight' % m], s['m%d_abundance' % m]) for m, n in enumerate(names)}
     table['H'] = _Element(s['weight_H'], 1.0)

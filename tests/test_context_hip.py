@@ -35,7 +35,8 @@ def test_piecewise_linear_1d_dropin_on_hip(hip_lib):
     context_cases.piecewise_linear_1d_dropin(None)
 
 
-@pytest.mark.parametrize('name', ['falc_cah.npz', 'falc_ca.npz', 'falc_ca_vlos.npz'])
+@pytest.mark.parametrize('name', ['falc_cah.npz', 'falc_ca.npz', 'falc_ca_vlos.npz', 'falc_c.npz', 'falc_fe.npz', 'falc_mg.npz',
+                                  'falc_all.npz'])
 def test_context_native_setup_chain_on_hip(name):
     context_cases.context_native_setup_chain(None, name)
 

@@ -73,7 +73,8 @@ def test_context_two_active_atoms_order_and_shapes(oracle_lib):
     context_cases.context_two_active_atoms_order_and_shapes(oracle_lib)
 
 
-@pytest.mark.parametrize('name', ['falc_cah.npz', 'falc_ca.npz', 'falc_ca_vlos.npz'])
+@pytest.mark.parametrize('name', ['falc_cah.npz', 'falc_ca.npz', 'falc_ca_vlos.npz', 'falc_c.npz', 'falc_fe.npz', 'falc_mg.npz',
+                                  'falc_all.npz'])
 def test_context_native_setup_chain(oracle_lib, name):
     context_cases.context_native_setup_chain(oracle_lib, name)
 

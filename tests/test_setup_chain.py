@@ -5,10 +5,11 @@ lsx_set_atomic_data / lsx_set_atmosphere.
 Pinned on what the reference itself computed for FALC and for a perturbed atmosphere (tests/golden/setup_falc.npz, written
 by make_golden.py setup from the unmodified reference: atomic_model.py:66-69, 300-345, 491-502; atomic_set.py:105-145;
 collisional_rates.py:10-96).  Tolerance 1e-13 relative (rates: relative to the largest rate of the depth, the small ones
-are differences of interpolated values)."""
+are differences of interpolated values; and entry by entry inside the bars of tests/setup_cases.py)."""
 import numpy as np
 import pytest
 
+import setup_cases
 from conftest import golden, relerr
 from lightspinner_amd import fixtures, atomdata, _capi
 from lightspinner_amd.problem import Engine, ColumnBlock
@@ -36,6 +37,8 @@ def _check(lib, tol=1e-13):
     e.set_atmosphere(0, lte_pops=True, **_atm(d, tags))
     vB, aD = e.get(_capi.LSX_VBROAD), e.get(_capi.LSX_ADAMP)
     nStar, Cr, n = e.get(_capi.LSX_NSTAR), e.get(_capi.LSX_C), e.get(_capi.LSX_N)
+    data = atomdata.from_fixture(d)
+    led = setup_cases.Ledger('%s setup_falc' % lib.backend)
     for c, t in enumerate(tags):
         lo = 0
         for a in range(2):
@@ -50,7 +53,9 @@ def _check(lib, tol=1e-13):
             Cref = d[pre + 'C'].reshape(36, -1)
             scale = np.abs(Cref).max(axis=0, keepdims=True)
             assert np.max(np.abs(Cr[c, o2:o2 + 36] - Cref) / scale) < tol, (t, a)
-            assert np.all(Cr[c, o2:o2 + 36] >= 0.0)
+            # and per entry, inside the bars of tests/setup_cases.py (the zeros the reference clamps exactly)
+            _, bar = setup_cases.rates_and_bars(data.atoms[a], d[t + '_temperature'], d[t + '_ne'], d[pre + 'nStar'])
+            setup_cases.check_rates(led, 'C', Cr[c, o2:o2 + 36].reshape(6, 6, -1), d[pre + 'C'], bar)
     # FALC column: the profiles built from the library's own damping are the reference's (falc_cah.npz holds t.phi, t.wphi)
     assert relerr(e.get(_capi.LSX_PHI, 0, 1)[0], block.phi[0]) < 3e-13
     assert relerr(e.get(_capi.LSX_WPHI, 0, 1)[0], block.wphi[0]) < 1e-13
@@ -109,8 +114,18 @@ def test_setup_chain_at_batch_size_feeds_the_hot_path(hip_lib, oracle_lib):
     oracle_lib.dll.lsx_oracle_set_threads(ora._h, 8)
     for what, tol in ((_capi.LSX_VBROAD, 1e-14), (_capi.LSX_ADAMP, 1e-13), (_capi.LSX_NSTAR, 1e-13), (_capi.LSX_WPHI, 1e-13), (_capi.LSX_PHI, 1e-12)):
         assert relerr(hip.get(what), ora.get(what)) < tol, what
-    Ch, Co = hip.get(_capi.LSX_C), ora.get(_capi.LSX_C)
+    Ch, Co, nS = hip.get(_capi.LSX_C), ora.get(_capi.LSX_C), ora.get(_capi.LSX_NSTAR)
     assert np.max(np.abs(Ch - Co) / np.abs(Co).max(axis=1, keepdims=True)) < 1e-13
+    # and per entry: each library inside the bars of tests/setup_cases.py around the reference's formulas on the oracle's nStar
+    data = atomdata.from_fixture(d)
+    led = setup_cases.Ledger('hip vs oracle, 48 columns')
+    for c in range(ncol):
+        for a in range(2):
+            o, o2 = prob.lev_off[a], prob.lev2_off[a]
+            Cx, bar = setup_cases.rates_and_bars(data.atoms[a], atm['temperature'][c], atm['ne'][c], nS[c, o:o + 6])
+            for C in (Ch, Co):
+                setup_cases.check_rates(led, 'C', C[c, o2:o2 + 36].reshape(6, 6, -1), Cx, bar)
+    led.report()
     # column 0 is the unperturbed FALC atmosphere: the reference's own numbers
     assert relerr(hip.get(_capi.LSX_NSTAR, 0, 1)[0], np.concatenate([d['atm0_a%d_nStar' % a] for a in range(2)])) < 1e-13
     for it in range(1, 7):
