@@ -196,6 +196,11 @@ class LsxLibrary:
         d.lsx_time_formal_sol.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _dp, _dp]
         d.lsx_algorithmic_bytes_per_column.argtypes = [C.c_void_p]
         d.lsx_algorithmic_bytes_per_column.restype = C.c_double
+        # entries of the HIP library alone (include/lsx_hip.h): bound where the library has them, never required
+        self.has_emergent_rays = hasattr(d, 'lsx_hip_emergent_rays')
+        if self.has_emergent_rays:
+            d.lsx_hip_emergent_rays.argtypes = [C.c_void_p, C.c_int32, _dp, C.c_int32, C.c_int32, _dp, C.c_size_t]
+            d.lsx_hip_emergent_rays.restype = C.c_int
 
     @property
     def backend(self):

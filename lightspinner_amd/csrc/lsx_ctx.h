@@ -103,6 +103,16 @@ struct lsx_ctx : lsxd::LsxPlan {        // the plan (lsx_plan.h: dimensions, tab
     int32_t* d_sa_levdZ = nullptr;
     bool have_atomic_data = false;
     double *d_vBroad = nullptr, *d_aDamp = nullptr;     // [col][Natoms][k], [col][Nlines][k]
+    // what the line profiles of a column were built from is KEPT (vBroad and aDamp above, and the line-of-sight velocity), whichever
+    // entry built them (lsx_set_line_profiles, lsx_set_atmosphere): the final pass at other angles re-evaluates ray-dependent
+    // profiles from it (lsx_rays.hip)
+    double* d_vlos = nullptr;            // [col][k], zero where none was given
+    uint8_t* d_prof_kind = nullptr;      // per column: 0 profiles handed over as arrays (or none yet), 1 built without, 2 with a velocity
+    std::vector<uint8_t> prof_kind;      // host copy of the same
+    bool atm_arrays = false;             // lsx_set_atmosphere has run: LSX_VBROAD / LSX_ADAMP can be read back
+    // column-independent tables of lsx_hip_emergent_rays, made on first use (lsx_rays.hip)
+    int32_t *d_rays_ptr = nullptr, *d_rays_tile = nullptr;
+    char* d_rays_ent = nullptr;
     // staging
     double* d_stage = nullptr;
     size_t stage_doubles = 0;
@@ -164,6 +174,7 @@ int upload(T** dptr, const std::vector<T>& v, hipStream_t st)
 int ensure_stage(lsx_ctx* c, size_t doubles);    // grow the context's staging buffer
 int rebuild_derived(lsx_ctx* c, size_t col0, size_t ncol);     // continuum g_ij tables + nStar ratios from (nStar, T)
 int profiles_from_device(lsx_ctx* c, size_t col0, size_t ncol, const double* dA, const double* dV, const double* dL);
+void profiles_handed_over(lsx_ctx* c, size_t col0, size_t ncol);    // these columns' profiles no longer come from kept inputs
 void mark_profiles_set(lsx_ctx* c, size_t col0, size_t ncol);
 
 } // namespace lsxd

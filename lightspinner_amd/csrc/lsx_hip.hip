@@ -20,6 +20,7 @@
 
 #include "lsx_ctx.h"
 #include "lsx_fast.h"
+#include "lsx_voigt.h"
 
 // A context launches up to six tile classes on streams of their own; with the HIP runtime's default of four hardware queues two
 // of them wait for the others.  The runtime reads GPU_MAX_HW_QUEUES when it initialises, i.e. at the process's first
@@ -126,40 +127,7 @@ __global__ void k_unpack_phi(const PhiBlock in, double* __restrict__ out, int lt
     }
 }
 
-// ---- Voigt function H(a, v) = Re w(v + i a), a > 0 (utils.py:13-15 calls scipy's wofz) ----
-// Trapezoid rule with step h = 1/2 on w(z) = (i/pi) int exp(-t^2)/(z - t) dt plus the residue of the pole the
-// contour crosses (Chiarella & Reichel 1968; Matta & Reichel 1971):
-//   H = (h a/pi) sum_n exp(-g_n^2) / ((v - g_n)^2 + a^2) + Re[ 2 exp(-z^2) / (1 -+ exp(-2 pi i z/h)) ]
-// on the grid g_n = n h (sign -) or (n + 1/2) h (sign +), whichever keeps v at least h/4 away from a node; error
-// ~ exp(-pi^2/h^2) = 7e-18.  Every term of the sum is positive (no cancellation in the far wings).
-// W: [2][28] = exp(-g_n^2) for n = -14 .. 13 on the two grids (host-computed).
-__device__ __forceinline__ double dev_voigt(double a, double v, const double* __restrict__ W)
-{
-    const double h = 0.5;
-    const double x = fabs(v);
-    const double t = x * 2.0, fr = t - floor(t);
-    const bool half = !(fr >= 0.25 && fr < 0.75);
-    const double shift = half ? 0.5 : 0.0;
-    const double* w = W + (half ? 28 : 0);
-    const double a2 = a * a;
-    double s = 0.0;
-#pragma unroll 4
-    for (int n = -14; n <= 13; ++n) {
-        const double d = x - ((double)n + shift) * h;
-        s += w[n + 14] / (d * d + a2);
-    }
-    double H = (h / M_PI) * a * s;
-    if (x < 27.0 && a < 2.0 * M_PI) {
-        // exp(-z^2) = exp(a^2 - x^2) (cos 2xa - i sin 2xa);  exp(-2 pi i z/h) = exp(4 pi a) (cos - i sin)(4 pi x)
-        double s1, c1, st, ct;
-        sincos(2.0 * x * a, &s1, &c1);
-        sincospi(4.0 * x, &st, &ct);
-        const double er = exp(a2 - x * x), E = exp(4.0 * M_PI * a), sg = half ? 1.0 : -1.0;
-        const double dr = 1.0 + sg * E * ct, di = -sg * E * st;
-        H += 2.0 * er * (c1 * dr - s1 * di) / (dr * dr + di * di);
-    }
-    return H;
-}
+// (the Voigt function itself: lsx_voigt.h, shared with the final pass at arbitrary angles)
 
 struct VoigtParams {
     int Ns, Nrays, ndir, Nlines, Natoms;
@@ -1224,6 +1192,34 @@ int profiles_from_device(lsx_ctx* c, size_t cc, size_t nb, const double* dA, con
         int rc = upload(&c->d_voigt_w, W, c->stream);
         if (rc) return rc;
     }
+    // keep what the profiles are built from: (Nlines + Natoms + 1) Nspace doubles per column (lsx_ctx.h)
+    {
+        const size_t nc = (size_t)c->ncol, NlA = (size_t)std::max(1, c->Nlines);
+        int rc;
+        if (!c->d_vBroad || !c->d_aDamp) {
+            if (c->d_vBroad) { (void)hipFree(c->d_vBroad); c->d_vBroad = nullptr; }
+            if (c->d_aDamp) { (void)hipFree(c->d_aDamp); c->d_aDamp = nullptr; }
+            if ((rc = dmalloc(&c->d_vBroad, nc * c->Natoms * Ns))) return rc;
+            if ((rc = dmalloc(&c->d_aDamp, nc * NlA * Ns))) { (void)hipFree(c->d_vBroad); c->d_vBroad = nullptr; return rc; }
+        }
+        if (!c->d_vlos) {
+            if ((rc = dmalloc(&c->d_vlos, nc * Ns))) return rc;
+            HIPCHK(hipMemsetAsync(c->d_vlos, 0, nc * Ns * sizeof(double), c->stream));
+        }
+        if (!c->d_prof_kind) {
+            if ((rc = dmalloc(&c->d_prof_kind, nc))) return rc;
+            HIPCHK(hipMemsetAsync(c->d_prof_kind, 0, nc, c->stream));
+            c->prof_kind.assign(nc, 0);
+        }
+        double* kA = c->d_aDamp + cc * NlA * Ns;
+        double* kV = c->d_vBroad + cc * c->Natoms * Ns;
+        if (dA != kA) HIPCHK(hipMemcpyAsync(kA, dA, nb * c->Nlines * Ns * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        if (dV != kV) HIPCHK(hipMemcpyAsync(kV, dV, nb * c->Natoms * Ns * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        if (dL) HIPCHK(hipMemcpyAsync(c->d_vlos + cc * Ns, dL, nb * Ns * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        else HIPCHK(hipMemsetAsync(c->d_vlos + cc * Ns, 0, nb * Ns * sizeof(double), c->stream));
+        HIPCHK(hipMemsetAsync(c->d_prof_kind + cc, dL ? 2 : 1, nb, c->stream));
+        std::fill(c->prof_kind.begin() + cc, c->prof_kind.begin() + cc + nb, (uint8_t)(dL ? 2 : 1));
+    }
     VoigtParams q{};
     q.Ns = Ns; q.Nlines = c->Nlines; q.Natoms = c->Natoms; q.wavelength = c->d_wavelength; q.muz = c->d_muz; q.wmu = c->d_wmu;
     q.W = c->d_voigt_w; q.aDamp = dA; q.vBroad = dV; q.vlos = dL;
@@ -1250,6 +1246,13 @@ int profiles_from_device(lsx_ctx* c, size_t cc, size_t nb, const double* dA, con
         HIPCHK(hipGetLastError());
     }
     return LSX_OK;
+}
+
+void profiles_handed_over(lsx_ctx* c, size_t col0, size_t ncol)
+{
+    if (!c->d_prof_kind) return;
+    (void)hipMemsetAsync(c->d_prof_kind + col0, 0, ncol, c->stream);
+    std::fill(c->prof_kind.begin() + col0, c->prof_kind.begin() + col0 + ncol, (uint8_t)0);
 }
 
 void mark_profiles_set(lsx_ctx* c, size_t col0, size_t ncol)
@@ -1281,7 +1284,7 @@ void lsx_destroy(lsx_ctx* c)
                     c->d_bgeta, c->d_sca, c->d_phi, c->d_E, c->d_corr, c->d_Psi3, c->d_J[0], c->d_J[1], c->d_I, c->d_Gpart, c->d_dJpart,
                     c->d_res, c->d_stage, c->d_debug, c->d_colmask, c->d_bgxchi, c->d_bgxeta, c->d_Psi2, c->d_fast_tiles, c->d_fast_rest, c->d_nsr, c->d_cont_li, c->d_cont_lj, c->d_exp2_tab, c->d_voigt_w, c->d_muz, c->d_wmu, c->d_optab, c->d_trans_row, c->d_fgtab, c->d_level_atom,
                     c->d_sa_atoms, c->d_sa_lines, c->d_sa_colls, c->d_sa_spl, c->d_sa_levE, c->d_sa_levg, c->d_sa_levnD, c->d_sa_levdZ,
-                    c->d_vBroad, c->d_aDamp};
+                    c->d_vBroad, c->d_aDamp, c->d_vlos, c->d_prof_kind, c->d_rays_ptr, c->d_rays_tile, c->d_rays_ent};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     for (int v = 0; v < LSX_FGC_LISTS; ++v) if (c->d_fast_cols[v]) (void)hipFree(c->d_fast_cols[v]);
@@ -1641,6 +1644,7 @@ int lsx_set_columns(lsx_ctx* c, int32_t col0, int32_t ncol, const lsx_columns* s
         HIPCHK(hipStreamSynchronize(c->stream)); // the staging buffer is re-used by the next sub-chunk
     }
 #undef TRY
+    profiles_handed_over(c, o, (size_t)ncol);
     for (int q = 0; q < ncol; ++q) {       // profiles of these columns: handed over, or still to come (lsx_set_line_profiles)
         const uint8_t v = (have_phi || !c->Nlines) ? 1 : 0;
         c->n_phi_set += (size_t)v - c->phi_set[o + q];
@@ -2227,7 +2231,7 @@ int lsx_get(lsx_ctx* c, int32_t what, int32_t col0, int32_t ncol, double* dst, s
     case LSX_WPHI: base = c->d_wphi; per = (size_t)c->Nlines * Ns; break;
     case LSX_VBROAD:
     case LSX_ADAMP:
-        if (!c->d_vBroad) return fail(LSX_EINVAL, "lsx_get: vBroad / aDamp exist after lsx_set_atmosphere only");
+        if (!c->d_vBroad || !c->atm_arrays) return fail(LSX_EINVAL, "lsx_get: vBroad / aDamp exist after lsx_set_atmosphere only");
         base = what == LSX_VBROAD ? c->d_vBroad : c->d_aDamp;
         per = (size_t)(what == LSX_VBROAD ? c->Natoms : std::max(1, c->Nlines)) * Ns;
         break;

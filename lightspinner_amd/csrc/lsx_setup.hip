@@ -401,6 +401,7 @@ int lsx_set_atmosphere(lsx_ctx* c, int32_t col0, int32_t ncol, const lsx_atmosph
         HIPCHK(hipStreamSynchronize(c->stream));                 // the staging buffer is re-used by the next sub-chunk
     }
     if (c->Nlines) mark_profiles_set(c, (size_t)col0, (size_t)ncol);
+    c->atm_arrays = true;
     return LSX_OK;
 }
 

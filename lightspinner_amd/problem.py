@@ -381,6 +381,20 @@ class Engine:
         self.lib.check(self.lib.dll.lsx_get(self._h, what, int(col0), int(ncol), _ptr(out), out.nbytes))
         return out
 
+    def emergent_rays(self, mus, col0=0, ncol=None):
+        """Emergent intensity at arbitrary viewing angles from what the engine holds (include/lsx_hip.h, lsx_hip_emergent_rays):
+        one final-pass formal solution of the up-going rays with direction cosines `mus` (each in (0, 1], any number of them)
+        for columns [col0, col0 + ncol), from the current populations and J.  Read-only.  -> [ncol][Nspect][nmu].
+        Only the HIP library computes it; there is no host version."""
+        if not getattr(self.lib, 'has_emergent_rays', False):
+            raise NotImplementedError('%s (%s) does not export lsx_hip_emergent_rays: emergent spectra at arbitrary angles are '
+                                      'computed by the HIP library only' % (self.lib.path, self.lib.backend))
+        mu = f64(np.atleast_1d(np.asarray(mus, dtype=np.float64)).reshape(-1))
+        ncol = self.ncol - int(col0) if ncol is None else int(ncol)
+        out = np.empty((max(ncol, 0), self.problem.Nspect, mu.shape[0]), dtype=np.float64)
+        self.lib.check(self.lib.dll.lsx_hip_emergent_rays(self._h, mu.shape[0], _ptr(mu), int(col0), ncol, _ptr(out), out.nbytes))
+        return out
+
     def gamma_of_atom(self, G, a):
         """view [ncol][Nl][Nl][Nspace] of atom a inside an LSX_GAMMA array"""
         p = self.problem

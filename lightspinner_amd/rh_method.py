@@ -433,6 +433,16 @@ class Context:
         self._results_changed(('J', 'I', 'Gamma'))
         return dJ
 
+    def compute_rays(self, mus=1.0):
+        """Emergent intensity at arbitrary viewing angles: what the reference computes with a Context on atmos.rays(mus)
+        (atmosphere.py:386-393) that holds these populations and this J, after one formal_sol_gamma_matrices().  A float
+        gives [Nspect], a sequence [Nspect][nmu].  Nothing of the context changes: ctx.I stays the quadrature's."""
+        self._cancel_lookahead()                  # (the library's J is the last accepted call's again)
+        self._push_host_edits()
+        scalar = np.ndim(mus) == 0
+        out = self._engine.emergent_rays(np.atleast_1d(np.asarray(mus, dtype=np.float64)))[0]
+        return out[:, 0] if scalar else out
+
     def stat_equil(self) -> float:
         """rh_method.py:710-745 -> max relative population change; populations are written back IN
         PLACE into the arrays that alias eqPops[...].pops (rh_method.py:412-416, response_fn.py:62)"""
