@@ -31,6 +31,8 @@ extern "C" {
  * context, nbytes that does not match, a column whose line profiles have not been set yet. */
 int lsx_hip_emergent_rays(lsx_ctx* ctx, int32_t nmu, const double* mu, int32_t col0, int32_t ncol, double* dst, size_t nbytes);
 
+/* Radiative rates Rij / Rji of every transition from what a context holds: lsx_hip_rates.h, included below. */
+
 /* GPU_MAX_HW_QUEUES=n for this process unless the caller has set it: call before the first HIP call. */
 int lsx_hip_request_hw_queues(int32_t n);
 
@@ -40,4 +42,7 @@ int lsx_hip_poison_lds(int32_t device, int32_t rounds);
 #ifdef __cplusplus
 }
 #endif
+
+#include "lsx_hip_rates.h"
+
 #endif /* LSX_HIP_H */

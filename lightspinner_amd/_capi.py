@@ -201,6 +201,12 @@ class LsxLibrary:
         if self.has_emergent_rays:
             d.lsx_hip_emergent_rays.argtypes = [C.c_void_p, C.c_int32, _dp, C.c_int32, C.c_int32, _dp, C.c_size_t]
             d.lsx_hip_emergent_rays.restype = C.c_int
+        self.has_radiative_rates = hasattr(d, 'lsx_hip_radiative_rates')
+        if self.has_radiative_rates:
+            d.lsx_hip_radiative_rates.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _dp, _dp, _dp, C.c_size_t]
+            d.lsx_hip_radiative_rates.restype = C.c_int
+            d.lsx_hip_radiative_rates_work_cap.argtypes = [C.c_void_p, C.c_size_t]
+            d.lsx_hip_radiative_rates_work_cap.restype = C.c_int
 
     @property
     def backend(self):

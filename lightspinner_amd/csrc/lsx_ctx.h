@@ -113,6 +113,11 @@ struct lsx_ctx : lsxd::LsxPlan {        // the plan (lsx_plan.h: dimensions, tab
     // column-independent tables of lsx_hip_emergent_rays, made on first use (lsx_rays.hip)
     int32_t *d_rays_ptr = nullptr, *d_rays_tile = nullptr;
     char* d_rays_ent = nullptr;
+    // ... and of lsx_hip_radiative_rates (lsx_rates.hip), with the pass's work arrays (allocated at first use, under rates_work_cap bytes)
+    int32_t *d_rates_ptr = nullptr, *d_rates_tile = nullptr, *d_rates_row = nullptr;
+    char* d_rates_ent = nullptr;
+    double* d_rates_work = nullptr;
+    size_t rates_work_doubles = 0, rates_work_cap = 0;      // cap 0: the default of include/lsx_hip_rates.h
     // staging
     double* d_stage = nullptr;
     size_t stage_doubles = 0;

@@ -172,6 +172,28 @@ class ColumnBlock:
                               for k in _COLUMN_FIELDS})
 
 
+class RadiativeRates:
+    """What Engine.radiative_rates returns: .Rij, .Rji, .Rji_ref, each [ncol][Ntrans][Nspace] (Context.compute_rates: one column,
+    [Ntrans][Nspace], with .transitions, the matching objects in the same order).
+    Rij = sum I Vij wlamu; Rji = sum (Uji + I Vji) wlamu, the physical downward rate; Rji_ref = sum (Uji + I Vij) wlamu, the
+    reference's rh_method.py:692 for one call from zero."""
+
+    def __init__(self, Rij, Rji, Rji_ref, transitions=None, populations=None):
+        self.Rij, self.Rji, self.Rji_ref = Rij, Rji, Rji_ref
+        self.transitions = transitions
+        self._populations = populations      # per transition (n_i, n_j), [Nspace] each
+
+    def net(self):
+        """n_j Rji - n_i Rij per transition and depth, [Ntrans][Nspace]: the net radiative bracket, from the populations the context
+        held when the rates were computed"""
+        if self._populations is None:
+            raise ValueError('net() needs the populations: use Context.compute_rates()')
+        out = np.empty_like(self.Rij)
+        for kr, (ni, nj) in enumerate(self._populations):
+            out[kr] = nj * self.Rji[kr] - ni * self.Rij[kr]
+        return out
+
+
 class Engine:
     """One lsx_ctx.  `lib=None` binds the HIP backend (and raises if it is not built)."""
     _serials = itertools.count(1)
@@ -394,6 +416,24 @@ class Engine:
         out = np.empty((max(ncol, 0), self.problem.Nspect, mu.shape[0]), dtype=np.float64)
         self.lib.check(self.lib.dll.lsx_hip_emergent_rays(self._h, mu.shape[0], _ptr(mu), int(col0), ncol, _ptr(out), out.nbytes))
         return out
+
+    def radiative_rates(self, col0=0, ncol=None, work_cap_bytes=None):
+        """Radiative rates of every transition from what the engine holds (include/lsx_hip_rates.h, lsx_hip_radiative_rates): one
+        formal solution over the engine's own rays from the current populations and J, for columns [col0, col0 + ncol).
+        Read-only; nothing is accumulated over calls.  -> RadiativeRates with .Rij, .Rji (physical: Vji in the stimulated term) and
+        .Rji_ref (the reference's rh_method.py:692 for one call), each [ncol][Ntrans][Nspace], transitions in table order.
+        work_cap_bytes: the cap of the pass's device work memory from this call on (None: unchanged; 0: the default).
+        Only the HIP library computes it; there is no host version."""
+        if not getattr(self.lib, 'has_radiative_rates', False):
+            raise NotImplementedError('%s (%s) does not export lsx_hip_radiative_rates: radiative rates are computed by the HIP '
+                                      'library only' % (self.lib.path, self.lib.backend))
+        if work_cap_bytes is not None:
+            self.lib.check(self.lib.dll.lsx_hip_radiative_rates_work_cap(self._h, int(work_cap_bytes)))
+        ncol = self.ncol - int(col0) if ncol is None else int(ncol)
+        shape = (max(ncol, 0), self.problem.Ntrans, self.problem.Nspace)
+        Rij, Rji, Rji_ref = (np.empty(shape, dtype=np.float64) for _ in range(3))
+        self.lib.check(self.lib.dll.lsx_hip_radiative_rates(self._h, int(col0), ncol, _ptr(Rij), _ptr(Rji), _ptr(Rji_ref), Rij.nbytes))
+        return RadiativeRates(Rij, Rji, Rji_ref)
 
     def gamma_of_atom(self, G, a):
         """view [ncol][Nl][Nl][Nspace] of atom a inside an LSX_GAMMA array"""

@@ -41,8 +41,10 @@ call is formal_sol_gamma_matrices() -- and it has not edited n or J in between -
 switches it off.
 
 Deliberate differences, all outside the numbers the drivers use:
-  * `t.Rij` / `t.Rji` are not produced (the reference accumulates them without ever zeroing or
-    reading them, rh_method.py:691-692); accessing them raises AttributeError.
+  * `t.Rij` / `t.Rji` are not attributes of the transitions (the reference accumulates them over
+    its calls without ever zeroing or reading them, rh_method.py:691-692); accessing them raises
+    AttributeError.  `Context.compute_rates()` computes the rates of one formal solution on demand
+    from what the context holds, with the reference's form of Rji and the physical one.
   * collisional rates are evaluated when the Context is built and whenever
     `update_collisions()` is called, not on every formal solution (they depend on the
     atmosphere only, rh_method.py:474-487).
@@ -53,7 +55,7 @@ import numpy as np
 
 from . import _capi, atomdata
 from . import constants as Const
-from .problem import Problem, Transition, ColumnBlock, Engine
+from .problem import Problem, Transition, ColumnBlock, Engine, RadiativeRates
 
 _KNOWN_COLLISIONS = ('Omega', 'CI', 'CE')
 
@@ -442,6 +444,20 @@ class Context:
         scalar = np.ndim(mus) == 0
         out = self._engine.emergent_rays(np.atleast_1d(np.asarray(mus, dtype=np.float64)))[0]
         return out[:, 0] if scalar else out
+
+    def compute_rates(self):
+        """Radiative rates of every transition (rh_method.py:691-692) as ONE formal solution gives them from these populations and
+        this J: -> an object with .Rij, .Rji, .Rji_ref, each [Ntrans][Nspace] in the order of `.transitions`
+        ([t for atom in activeAtoms for t in atom.trans]), and .net() = n_j Rji - n_i Rij, the net radiative bracket.
+        Rji is the physical downward rate (Vji in the stimulated term); Rji_ref is the reference's line 692 (Vij there), which on a
+        fresh context is the reference's t.Rji after its first call.  The reference accumulates over its calls; this does not.
+        Nothing of the context changes."""
+        self._cancel_lookahead()                  # (the library's J is the last accepted call's again)
+        self._push_host_edits()
+        r = self._engine.radiative_rates()
+        trans = [t for a in self.activeAtoms for t in a.trans]
+        pops = [(np.array(t.atom.n[t.i], dtype=np.float64), np.array(t.atom.n[t.j], dtype=np.float64)) for t in trans]
+        return RadiativeRates(r.Rij[0], r.Rji[0], r.Rji_ref[0], transitions=trans, populations=pops)
 
     def stat_equil(self) -> float:
         """rh_method.py:710-745 -> max relative population change; populations are written back IN
