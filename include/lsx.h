@@ -40,7 +40,13 @@ enum {
     LSX_EINVAL = 1,      /* bad argument / inconsistent descriptor                  */
     LSX_EDEVICE = 2,     /* HIP runtime error (message carries hipGetErrorString)    */
     LSX_ESINGULAR = 3,   /* singular statistical-equilibrium system (cf. LinAlgError,
-                            rh_method.py:739); populations of that (col,k) untouched */
+                            rh_method.py:739); populations of that (col,k) untouched.
+                            A system that holds a NaN is refused in the same way: the pivot search
+                            meets it on a diagonal (the reference's scipy.linalg.solve refuses it
+                            too, check_finite).  Every other system is solved and enters
+                            LSX_DPOPS_COL as usual.  The message names the first such system in the
+                            reference's order: lowest column, then atom, then depth
+                            (tests/test_stat_equil_systems.py)                                   */
     /* 4 is unused: non-finite values are not an error, they propagate through dJ exactly as in
        the reference (numpy max, rh_method.py:705-706)                                            */
     LSX_EUNSUPPORTED = 5 /* valid request this build cannot run (e.g. Nrays > 8)     */

@@ -786,12 +786,13 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(NLC ==
     fast_gamma_cols_rows<NLC, 6, 2, true>(f, f.fast_tiles[blockIdx.y], (long)blockIdx.x * 2 * LSX_FGC_ROWS, (long)f.ncol * f.Nspace, sm);
 }
 
-// singular system at (column, depth) = gid, atom: the flag keeps the FIRST one in (column, depth, atom) order --
-// one order-independent 64-bit atomicMax of (2^48 - key), 0 = none -- for lsx_last_error (cf. LinAlgError, rh_method.py:739)
+// singular system at (column, atom, depth): the flag keeps the FIRST one in that order, the one the reference raises on (it walks
+// the atoms outside the depths, rh_method.py:720-739, and the columns one after the other) -- one order-independent 64-bit
+// atomicMax of (2^48 - key), key = (column << 8 | atom) Nspace + depth, 0 = none -- for lsx_last_error (cf. LinAlgError)
 #define LSX_SING_BASE (1ull << 48)
-__device__ __forceinline__ void flag_singular(unsigned long long* flag, long gid, int atom)
+__device__ __forceinline__ void flag_singular(unsigned long long* flag, int col, int atom, int k, int Ns)
 {
-    atomicMax(flag, LSX_SING_BASE - (((unsigned long long)gid << 8) | (unsigned)atom));
+    atomicMax(flag, LSX_SING_BASE - ((((unsigned long long)col << 8) | (unsigned)atom) * (unsigned long long)Ns + (unsigned)k));
 }
 
 __device__ __forceinline__ void atomic_max_nonneg(double* addr, double v)
@@ -856,7 +857,7 @@ __global__ void k_stat_equil(const double* __restrict__ Gamma, const double* __r
             for (int i = j + 1; i < Nl; ++i) A[(i + q * Nl) * nt] -= A[(i + j * Nl) * nt] * ajq;
         }
     }
-    if (sing) { flag_singular(singular, gid, atom); return; }
+    if (sing) { flag_singular(singular, col, atom, k, Ns); return; }
     for (int j = 0; j < Nl; ++j)
         for (int i = j + 1; i < Nl; ++i) b[i * nt] -= A[(i + j * Nl) * nt] * b[j * nt];
     for (int j = Nl - 1; j >= 0; --j) {
@@ -974,7 +975,7 @@ k_stat_equil_reg(const double* __restrict__ Gamma, const double* __restrict__ nT
             for (int i = j + 1; i < NL; ++i) a[i][q] -= a[i][j] * ajq;
         }
     }
-    if (sing) { flag_singular(singular, gid, atom); return; }
+    if (sing) { flag_singular(singular, col, atom, k, Ns); return; }
 #pragma unroll
     for (int j = 0; j < NL; ++j)
 #pragma unroll
@@ -2183,11 +2184,10 @@ int lsx_sync(lsx_ctx* c, double* dJ, double* dP)
 
 static int singular_error(lsx_ctx* c, unsigned long long sing)
 {
-    const unsigned long long key = LSX_SING_BASE - sing;
-    const long gid = (long)(key >> 8);
+    const unsigned long long key = LSX_SING_BASE - sing, ca = key / (unsigned long long)c->Nspace;      // flag_singular
     return fail(LSX_ESINGULAR, "stat_equil: singular matrix at column %ld, depth %ld, atom %d (the first such system; cf. "
                                "LinAlgError at rh_method.py:739); its populations are left untouched",
-                gid / c->Nspace, gid % c->Nspace, (int)(key & 0xff));
+                (long)(ca >> 8), (long)(key % (unsigned long long)c->Nspace), (int)(ca & 0xff));
 }
 
 int lsx_monitors(lsx_ctx* c, double* dst)

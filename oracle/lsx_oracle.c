@@ -1276,7 +1276,7 @@ int lsx_fetch_populations(lsx_ctx* c, double* dst, size_t nbytes)
 
 /* dense solve A x = b, A column-major N x N, LU with partial pivoting in the order
  * of LAPACK dgetf2 + dgetrs (what scipy.linalg.solve -> dgesv does, rh_method.py:739).
- * returns 0 ok, 1 singular. */
+ * returns 0 ok, 1 singular or not finite. */
 static int gesv(int N, double* A, double* b)
 {
     for (int j = 0; j < N; ++j) {
@@ -1286,7 +1286,8 @@ static int gesv(int N, double* A, double* b)
             double v = fabs(A[i + j * N]);
             if (v > amax) { amax = v; p = i; }
         }
-        if (A[p + j * N] == 0.0) return 1;
+        if (A[p + j * N] == 0.0 || amax != amax) return 1; /* a NaN anywhere ends on a diagonal: the system is refused like a singular
+                                                             * one (scipy.linalg.solve refuses it too: check_finite) */
         if (p != j) {
             for (int q = 0; q < N; ++q) { double t = A[j + q * N]; A[j + q * N] = A[p + q * N]; A[p + q * N] = t; }
             double t = b[j]; b[j] = b[p]; b[p] = t;
