@@ -33,6 +33,9 @@ int lsx_hip_emergent_rays(lsx_ctx* ctx, int32_t nmu, const double* mu, int32_t c
 
 /* Radiative rates Rij / Rji of every transition from what a context holds: lsx_hip_rates.h, included below. */
 
+/* Opacity, source function, optical depth, intensity and contribution function at every depth along arbitrary rays:
+ * lsx_hip_depth.h, included below. */
+
 /* GPU_MAX_HW_QUEUES=n for this process unless the caller has set it: call before the first HIP call. */
 int lsx_hip_request_hw_queues(int32_t n);
 
@@ -44,5 +47,6 @@ int lsx_hip_poison_lds(int32_t device, int32_t rounds);
 #endif
 
 #include "lsx_hip_rates.h"
+#include "lsx_hip_depth.h"
 
 #endif /* LSX_HIP_H */

@@ -207,6 +207,13 @@ class LsxLibrary:
             d.lsx_hip_radiative_rates.restype = C.c_int
             d.lsx_hip_radiative_rates_work_cap.argtypes = [C.c_void_p, C.c_size_t]
             d.lsx_hip_radiative_rates_work_cap.restype = C.c_int
+        self.has_depth_rays = hasattr(d, 'lsx_hip_depth_rays')         # include/lsx_hip_depth.h
+        if self.has_depth_rays:
+            d.lsx_hip_depth_rays.argtypes = [C.c_void_p, C.c_int32, _dp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                             _dp, _dp, _dp, _dp, _dp, _dp, C.c_size_t, C.c_size_t]
+            d.lsx_hip_depth_rays.restype = C.c_int
+            d.lsx_hip_depth_rays_work_cap.argtypes = [C.c_void_p, C.c_size_t]
+            d.lsx_hip_depth_rays_work_cap.restype = C.c_int
 
     @property
     def backend(self):

@@ -118,6 +118,11 @@ struct lsx_ctx : lsxd::LsxPlan {        // the plan (lsx_plan.h: dimensions, tab
     char* d_rates_ent = nullptr;
     double* d_rates_work = nullptr;
     size_t rates_work_doubles = 0, rates_work_cap = 0;      // cap 0: the default of include/lsx_hip_rates.h
+    // ... and of lsx_hip_depth_rays (lsx_depth.hip), with the arrays of a pass (allocated at first use, under depth_work_cap bytes)
+    int32_t *d_depth_ptr = nullptr, *d_depth_tile = nullptr;
+    char* d_depth_ent = nullptr;
+    double* d_depth_work = nullptr;
+    size_t depth_work_doubles = 0, depth_work_cap = 0;      // cap 0: the default of include/lsx_hip_depth.h
     // staging
     double* d_stage = nullptr;
     size_t stage_doubles = 0;

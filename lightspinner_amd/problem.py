@@ -194,6 +194,18 @@ class RadiativeRates:
         return out
 
 
+class DepthRays:
+    """What Engine.depth_rays returns: .chi, .S, .tau, .I, .contrib, each [ncol][nmu][Nspace][nla] (the wavelength runs fastest), and
+    .z_tau1 [ncol][nmu][nla], for the up-going rays with direction cosines .mus and the wavelengths [.la0, .la0 + nla) of the merged
+    grid; an array that was not asked for is None.  Context.compute_depth_rays drops the column axis (and the angle axis for a
+    scalar mu).  Definitions: include/lsx_hip_depth.h."""
+    FIELDS = ('chi', 'S', 'tau', 'I', 'contrib', 'z_tau1')
+
+    def __init__(self, mus, la0, chi=None, S=None, tau=None, I=None, contrib=None, z_tau1=None):
+        self.mus, self.la0 = mus, int(la0)
+        self.chi, self.S, self.tau, self.I, self.contrib, self.z_tau1 = chi, S, tau, I, contrib, z_tau1
+
+
 class Engine:
     """One lsx_ctx.  `lib=None` binds the HIP backend (and raises if it is not built)."""
     _serials = itertools.count(1)
@@ -434,6 +446,32 @@ class Engine:
         Rij, Rji, Rji_ref = (np.empty(shape, dtype=np.float64) for _ in range(3))
         self.lib.check(self.lib.dll.lsx_hip_radiative_rates(self._h, int(col0), ncol, _ptr(Rij), _ptr(Rji), _ptr(Rji_ref), Rij.nbytes))
         return RadiativeRates(Rij, Rji, Rji_ref)
+
+    def depth_rays(self, mus, la0=0, nla=None, col0=0, ncol=None, what=DepthRays.FIELDS, work_cap_bytes=None):
+        """Opacity, source function, optical depth, intensity and contribution function at every depth along the up-going rays with
+        direction cosines `mus`, and the height of tau = 1 (include/lsx_hip_depth.h, lsx_hip_depth_rays), for columns
+        [col0, col0 + ncol) and the wavelengths [la0, la0 + nla) of the merged grid (nla None: to the end of the grid), from the
+        current populations and J.  Read-only.  what: the arrays wanted, of 'chi', 'S', 'tau', 'I', 'contrib', 'z_tau1'.
+        work_cap_bytes: the cap of the pass's device memory from this call on (None: unchanged; 0: the default).
+        -> DepthRays.  Only the HIP library computes it; there is no host version."""
+        if not getattr(self.lib, 'has_depth_rays', False):
+            raise NotImplementedError('%s (%s) does not export lsx_hip_depth_rays: the depth-resolved final pass is computed by the '
+                                      'HIP library only' % (self.lib.path, self.lib.backend))
+        what = (what,) if isinstance(what, str) else tuple(what)
+        unknown = [w for w in what if w not in DepthRays.FIELDS]
+        if unknown:
+            raise ValueError('depth_rays: unknown array(s) %s; there are %s' % (unknown, ', '.join(DepthRays.FIELDS)))
+        if work_cap_bytes is not None:
+            self.lib.check(self.lib.dll.lsx_hip_depth_rays_work_cap(self._h, int(work_cap_bytes)))
+        mu = f64(np.atleast_1d(np.asarray(mus, dtype=np.float64)).reshape(-1))
+        ncol = self.ncol - int(col0) if ncol is None else int(ncol)
+        nla = self.problem.Nspect - int(la0) if nla is None else int(nla)
+        shape = (max(ncol, 0), mu.shape[0], self.problem.Nspace, max(nla, 0))
+        out = {w: np.empty(shape[:2] + shape[3:] if w == 'z_tau1' else shape, dtype=np.float64) for w in what}
+        ptr = [_ptr(out[w]) if w in out else None for w in DepthRays.FIELDS]
+        self.lib.check(self.lib.dll.lsx_hip_depth_rays(self._h, mu.shape[0], _ptr(mu), int(col0), ncol, int(la0), nla, *ptr,
+                                                       int(np.prod(shape)) * 8, int(np.prod(shape[:2] + shape[3:])) * 8))
+        return DepthRays(mu, la0, **out)
 
     def gamma_of_atom(self, G, a):
         """view [ncol][Nl][Nl][Nspace] of atom a inside an LSX_GAMMA array"""

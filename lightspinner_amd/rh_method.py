@@ -55,7 +55,7 @@ import numpy as np
 
 from . import _capi, atomdata
 from . import constants as Const
-from .problem import Problem, Transition, ColumnBlock, Engine, RadiativeRates
+from .problem import Problem, Transition, ColumnBlock, Engine, RadiativeRates, DepthRays
 
 _KNOWN_COLLISIONS = ('Omega', 'CI', 'CE')
 
@@ -444,6 +444,25 @@ class Context:
         scalar = np.ndim(mus) == 0
         out = self._engine.emergent_rays(np.atleast_1d(np.asarray(mus, dtype=np.float64)))[0]
         return out[:, 0] if scalar else out
+
+    def compute_depth_rays(self, mus=1.0, la0=0, nla=None, transition=None):
+        """WHERE the emergent intensity forms: opacity chi, source function S, optical depth tau, up-going intensity I and the
+        contribution function chi S exp(-tau) / mu at every depth along the rays with direction cosines `mus`, and the height at
+        which tau = 1, for the wavelengths [la0, la0 + nla) of spect.wavelength -- what the reference builds inside a formal
+        solution on atmos.rays(mus) and throws away (rh_method.py:601-638).  transition: one of the context's transitions (the
+        object, or its place in [t for atom in activeAtoms for t in atom.trans]) selects that transition's own window instead.
+        -> an object with .chi .S .tau .I .contrib, each [nmu][Nspace][nla] ([Nspace][nla] for a float mu), .z_tau1 [nmu][nla]
+        ([nla]), .mus, .la0.  Nothing of the context changes."""
+        self._cancel_lookahead()                  # (the library's J is the last accepted call's again)
+        self._push_host_edits()
+        if transition is not None:
+            if isinstance(transition, (int, np.integer)):
+                transition = [t for a in self.activeAtoms for t in a.trans][int(transition)]
+            la0, nla = int(transition.Nblue), int(transition.wavelength.shape[0])
+        scalar = np.ndim(mus) == 0
+        r = self._engine.depth_rays(np.atleast_1d(np.asarray(mus, dtype=np.float64)), la0=la0, nla=nla)
+        pick = (lambda a: a[0, 0]) if scalar else (lambda a: a[0])
+        return DepthRays(r.mus, r.la0, **{w: pick(getattr(r, w)) for w in DepthRays.FIELDS})
 
     def compute_rates(self):
         """Radiative rates of every transition (rh_method.py:691-692) as ONE formal solution gives them from these populations and
