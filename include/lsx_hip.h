@@ -36,6 +36,8 @@ int lsx_hip_emergent_rays(lsx_ctx* ctx, int32_t nmu, const double* mu, int32_t c
 /* Opacity, source function, optical depth, intensity and contribution function at every depth along arbitrary rays:
  * lsx_hip_depth.h, included below. */
 
+/* Ng acceleration of the MALI loop, per column, opt-in: lsx_hip_ng.h, included below. */
+
 /* GPU_MAX_HW_QUEUES=n for this process unless the caller has set it: call before the first HIP call. */
 int lsx_hip_request_hw_queues(int32_t n);
 
@@ -48,5 +50,6 @@ int lsx_hip_poison_lds(int32_t device, int32_t rounds);
 
 #include "lsx_hip_rates.h"
 #include "lsx_hip_depth.h"
+#include "lsx_hip_ng.h"
 
 #endif /* LSX_HIP_H */

@@ -214,6 +214,13 @@ class LsxLibrary:
             d.lsx_hip_depth_rays.restype = C.c_int
             d.lsx_hip_depth_rays_work_cap.argtypes = [C.c_void_p, C.c_size_t]
             d.lsx_hip_depth_rays_work_cap.restype = C.c_int
+        self.has_ng = hasattr(d, 'lsx_hip_ng_configure')               # include/lsx_hip_ng.h
+        if self.has_ng:
+            ip32 = C.POINTER(C.c_int32)
+            d.lsx_hip_ng_configure.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+            d.lsx_hip_ng_configure.restype = C.c_int
+            d.lsx_hip_ng_state.argtypes = [C.c_void_p, C.c_int32, C.c_int32, ip32, ip32, ip32, _dp]
+            d.lsx_hip_ng_state.restype = C.c_int
 
     @property
     def backend(self):

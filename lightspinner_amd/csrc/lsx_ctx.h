@@ -123,6 +123,12 @@ struct lsx_ctx : lsxd::LsxPlan {        // the plan (lsx_plan.h: dimensions, tab
     char* d_depth_ent = nullptr;
     double* d_depth_work = nullptr;
     size_t depth_work_doubles = 0, depth_work_cap = 0;      // cap 0: the default of include/lsx_hip_depth.h
+    // Ng acceleration of the populations (lsx_ng.hip, include/lsx_hip_ng.h): off (order 0) unless lsx_hip_ng_configure turns it on
+    int ng_order = 0, ng_delay = 0;
+    double* d_ng_hist = nullptr;         // [col][order + 2][NLtot][k]: the stored populations, slot = the column's counter
+    int32_t* d_ng_state = nullptr;       // [3][ncol]: counter, steps taken, steps rejected
+    double* d_ng_coef = nullptr;         // [col][Natoms][2]: the coefficients of the last step taken
+    int* d_ng_off = nullptr;             // [Natoms + 1]: where each atom's levels x depths start in a column's populations
     // staging
     double* d_stage = nullptr;
     size_t stage_doubles = 0;
@@ -186,5 +192,9 @@ int rebuild_derived(lsx_ctx* c, size_t col0, size_t ncol);     // continuum g_ij
 int profiles_from_device(lsx_ctx* c, size_t col0, size_t ncol, const double* dA, const double* dV, const double* dL);
 void profiles_handed_over(lsx_ctx* c, size_t col0, size_t ncol);    // these columns' profiles no longer come from kept inputs
 void mark_profiles_set(lsx_ctx* c, size_t col0, size_t ncol);
+// Ng acceleration (lsx_ng.hip); all three do nothing while it is off
+int ng_enqueue(lsx_ctx* c);                              // the step behind a statistical equilibrium, on the context's stream
+int ng_reset(lsx_ctx* c, size_t col0, size_t ncol);      // these columns' populations have been replaced: their history is discarded
+void ng_free(lsx_ctx* c);
 
 } // namespace lsxd

@@ -1311,6 +1311,7 @@ void lsx_destroy(lsx_ctx* c)
     if (c->evB) (void)hipEventDestroy(c->evB);
     if (c->h_pinned) (void)hipHostFree(c->h_pinned);
     if (c->h_n) (void)hipHostFree(c->h_n);
+    ng_free(c);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -1657,6 +1658,7 @@ int lsx_set_columns(lsx_ctx* c, int32_t col0, int32_t ncol, const lsx_columns* s
     HIPCHK(hipMemsetAsync(c->d_J[c->jcur] + o * c->til_col, 0, (size_t)ncol * c->til_col * 8, c->stream));
     HIPCHK(hipMemsetAsync(c->d_I + o * Nspect * c->Nrays, 0, (size_t)ncol * Nspect * c->Nrays * 8, c->stream));
     HIPCHK(hipMemsetAsync(c->d_Gamma + o * c->NL2tot * Ns, 0, (size_t)ncol * c->NL2tot * Ns * 8, c->stream));
+    if (c->ng_order && (rc = ng_reset(c, o, (size_t)ncol))) return rc;       // new populations: the Ng history of these columns is void
     HIPCHK(hipStreamSynchronize(c->stream));
     return LSX_OK;
 }
@@ -2047,6 +2049,11 @@ int lsx_stat_equil_async(lsx_ctx* c)
 #undef SE_REG
         HIPCHK(hipGetLastError());
     }
+    // Ng acceleration, where configured (lsx_ng.hip): one launch behind the solves, ahead of any read-back of this call's results
+    if (c->ng_order) {
+        const int rc = ng_enqueue(c);
+        if (rc) return rc;
+    }
     c->se_pending = true;
     c->optab_fresh = false;           // the populations have changed (the table is rebuilt behind the read-back of this call's monitors: lsx_sync)
     return LSX_OK;
@@ -2293,6 +2300,10 @@ int lsx_set(lsx_ctx* c, int32_t what, int32_t col0, int32_t ncol, const double* 
     if (nbytes != per * ncol * 8) return fail(LSX_EINVAL, "lsx_set: nbytes does not match the item's shape");
     if (what == LSX_N) {
         HIPCHK(hipMemcpyAsync(c->d_n + per * col0, src, nbytes, hipMemcpyHostToDevice, c->stream));
+        if (c->ng_order) {                  // new populations: the Ng history of these columns is void
+            const int rc = ng_reset(c, (size_t)col0, (size_t)ncol);
+            if (rc) return rc;
+        }
         HIPCHK(hipStreamSynchronize(c->stream));
         return LSX_OK;
     }
@@ -2471,6 +2482,8 @@ static std::string effective_options(const lsx_ctx* c)
     s += ";classes=" + plan_class_string(*c);
     // which library this is: two ranks with different builds must not pass for alike (parallel.check_same_options)
     s += ";abi=" + std::to_string(LSX_ABI_VERSION) + ";build=" + lsx_build_id();
+    // Ng acceleration changes what every iteration computes: named when on, and only then (off: the string is what it always was)
+    if (c->ng_order) s += ";ng=" + std::to_string(c->ng_order) + "," + std::to_string(c->ng_delay);
     return s;
 }
 

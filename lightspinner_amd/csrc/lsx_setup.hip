@@ -398,6 +398,7 @@ int lsx_set_atmosphere(lsx_ctx* c, int32_t col0, int32_t ncol, const lsx_atmosph
         HIPCHK(hipGetLastError());
         if (c->Nlines && (rc = profiles_from_device(c, cc, nb, q.aDamp, q.vBroad, s->vlos ? dVl : nullptr))) return rc;
         if ((rc = rebuild_derived(c, cc, nb))) return rc;        // g_ij factors follow (nStar, T)
+        if (s->lte_pops && c->ng_order && (rc = ng_reset(c, cc, nb))) return rc;      // new populations: their Ng history is void
         HIPCHK(hipStreamSynchronize(c->stream));                 // the staging buffer is re-used by the next sub-chunk
     }
     if (c->Nlines) mark_profiles_set(c, (size_t)col0, (size_t)ncol);

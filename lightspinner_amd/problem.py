@@ -206,6 +206,37 @@ class DepthRays:
         self.chi, self.S, self.tau, self.I, self.contrib, self.z_tau1 = chi, S, tau, I, contrib, z_tau1
 
 
+class NgOptions:
+    """Ng acceleration of the MALI loop (include/lsx_hip_ng.h): order 1 or 2 (0: off), delay >= 0 statistical equilibria that pass
+    before the first population vector is stored.  What Context(ng=...) and run_response_function(ng=...) take."""
+    __slots__ = ('order', 'delay')
+
+    def __init__(self, order=2, delay=0):
+        order, delay = int(order), int(delay)
+        if order not in (0, 1, 2):
+            raise ValueError('NgOptions: order %d; 1 and 2 are offered, 0 switches it off' % order)
+        if delay < 0:
+            raise ValueError('NgOptions: delay %d is negative' % delay)
+        self.order, self.delay = order, delay
+
+    def __eq__(self, other):
+        return isinstance(other, NgOptions) and (self.order, self.delay) == (other.order, other.delay)
+
+    def __hash__(self):
+        return hash((self.order, self.delay))
+
+    def __repr__(self):
+        return 'NgOptions(order=%d, delay=%d)' % (self.order, self.delay)
+
+
+class NgState:
+    """What Engine.ng_state returns: .stored, .applied, .rejected, int32 [ncol]; .coef [ncol][Natoms][2], the coefficients of each
+    column's last step taken (include/lsx_hip_ng.h)"""
+
+    def __init__(self, stored, applied, rejected, coef):
+        self.stored, self.applied, self.rejected, self.coef = stored, applied, rejected, coef
+
+
 class Engine:
     """One lsx_ctx.  `lib=None` binds the HIP backend (and raises if it is not built)."""
     _serials = itertools.count(1)
@@ -472,6 +503,33 @@ class Engine:
         self.lib.check(self.lib.dll.lsx_hip_depth_rays(self._h, mu.shape[0], _ptr(mu), int(col0), ncol, int(la0), nla, *ptr,
                                                        int(np.prod(shape)) * 8, int(np.prod(shape[:2] + shape[3:])) * 8))
         return DepthRays(mu, la0, **out)
+
+    def configure_ng(self, order=2, delay=0):
+        """Ng acceleration of the populations behind every stat_equil of this engine (include/lsx_hip_ng.h, lsx_hip_ng_configure):
+        order 1 or 2, 0 switches it off; `delay` statistical equilibria pass before the first vector is stored.  Also takes an
+        NgOptions (or None: off) as `order`.  Every column's history and counters are reset.
+        Only the HIP library has it; there is no host version."""
+        if not getattr(self.lib, 'has_ng', False):
+            raise NotImplementedError('%s (%s) does not export lsx_hip_ng_configure: Ng acceleration is done by the HIP library '
+                                      'only' % (self.lib.path, self.lib.backend))
+        if order is None:
+            order, delay = 0, 0
+        elif isinstance(order, NgOptions):
+            order, delay = order.order, order.delay
+        self.lib.check(self.lib.dll.lsx_hip_ng_configure(self._h, int(order), int(delay)))
+
+    def ng_state(self, col0=0, ncol=None) -> NgState:
+        """the Ng state of columns [col0, col0 + ncol) (include/lsx_hip_ng.h, lsx_hip_ng_state)"""
+        if not getattr(self.lib, 'has_ng', False):
+            raise NotImplementedError('%s (%s) does not export lsx_hip_ng_state: Ng acceleration is done by the HIP library only'
+                                      % (self.lib.path, self.lib.backend))
+        ncol = self.ncol - int(col0) if ncol is None else int(ncol)
+        st, ap, rj = (np.zeros(max(ncol, 0), dtype=np.int32) for _ in range(3))
+        coef = np.zeros((max(ncol, 0), self.problem.Natoms, 2), dtype=np.float64)
+        ip32 = C.POINTER(C.c_int32)
+        self.lib.check(self.lib.dll.lsx_hip_ng_state(self._h, int(col0), ncol, st.ctypes.data_as(ip32), ap.ctypes.data_as(ip32),
+                                                     rj.ctypes.data_as(ip32), _ptr(coef)))
+        return NgState(st, ap, rj, coef)
 
     def gamma_of_atom(self, G, a):
         """view [ncol][Nl][Nl][Nspace] of atom a inside an LSX_GAMMA array"""

@@ -114,7 +114,7 @@ def index_deltas(fixture: dict) -> dict:
 
 
 def run_response_function(prob: Problem, base: ColumnBlock, fixture: dict, ks, lib=None, device=0, mu_index=-1, log=None,
-                          rank=0, world=1, all_done=None, gather=None, stream=None):
+                          rank=0, world=1, all_done=None, gather=None, stream=None, ng=None):
     """response_fn.py:11-74 as two batched solves: (1) the base column to convergence (test.py:20-29 loop, per-column
     stopping rule), (2) the 2 x len(ks) perturbed columns, warm started from the base populations
     (response_fn.py:33), every column with its own stopping rule, then rf[la, k] = (I+ - I-) / I_base at `mu_index`
@@ -125,11 +125,16 @@ def run_response_function(prob: Problem, base: ColumnBlock, fixture: dict, ks, l
     broadcast of the warm-start populations is needed -- and iterates its shard until ALL ranks are done
     (all_done = parallel.AllDone(): logical AND, the per-column stopping rule needs no other exchange);
     gather(I_local [n_local][Nspect][Nrays], n_iter_local) -> (I of all columns, n_iter of all columns) on every rank
-    (e.g. torch.distributed.all_gather_object).  A rank with an empty shard still takes part in the collectives."""
+    (e.g. torch.distributed.all_gather_object).  A rank with an empty shard still takes part in the collectives.
+
+    ng (problem.NgOptions, default None: off): Ng acceleration of the populations in both solves (include/lsx_hip_ng.h); the
+    options check of a sharded job then covers it."""
     from . import _capi, drivers
     from .parallel import shard_columns
     from .problem import Engine
     e0 = Engine(prob, 1, device=device, lib=lib, stream=stream)
+    if ng is not None and ng.order:
+        e0.configure_ng(ng)
     e0.set_columns(0, base.slice(0, 1))
     # (one column: its own stopping rule IS the global one -- the engine loop, which keeps the next formal solution enqueued while the
     # host reads the monitors where the library says that pays, lsx_prefers_lookahead; the same iterations and bits)
@@ -150,6 +155,8 @@ def run_response_function(prob: Problem, base: ColumnBlock, fixture: dict, ks, l
         batch = apply_deltas(prob, base, [(index.get((k, tag), {}), k) for k, tag in mine], start_n=n_base)
         # the kernel choice belongs to the problem -- all 2 len(ks) perturbed columns -- not to this rank's shard of it
         eng = Engine(prob, batch.ncol, device=device, lib=lib, stream=stream, policy_columns=len(jobs))
+        if ng is not None and ng.order:
+            eng.configure_ng(ng)
         for a in range(0, batch.ncol, 64):
             eng.set_columns(a, batch.slice(a, min(batch.ncol, a + 64)))
         n_iter = drivers.iterate_mali_columns(eng, log=log, all_done=all_done)

@@ -213,7 +213,7 @@ class Context:
     """rh_method.py:490-745 on the GPU."""
 
     def __init__(self, atmos, spect, eqPops, background, device: int = 0, stream=None, lib=None, setup: str = 'auto',
-                 formal_solver: str = 'linear', readback: str = 'lazy', lookahead: Optional[bool] = None):
+                 formal_solver: str = 'linear', readback: str = 'lazy', lookahead: Optional[bool] = None, *, ng=None):
         self.atmos = atmos
         self.atmos.nondimensionalise()
         self.spect = spect
@@ -265,6 +265,8 @@ class Context:
         self._engine = Engine(self.problem, 1, device=device, stream=stream, lib=lib)
         if formal_solver != 'linear':          # 'parabolic': the monotonic piecewise-parabolic rule (include/lsx.h, N4; not in the reference)
             self._engine.set_formal_solver(formal_solver)
+        if ng is not None and ng.order:         # problem.NgOptions: Ng acceleration behind every stat_equil (include/lsx_hip_ng.h)
+            self._engine.configure_ng(ng)
         self._cache = {}
         if setup == 'native':
             in_table = lambda m, l: _contains(spect.transitions, l)
