@@ -38,6 +38,8 @@ int lsx_hip_emergent_rays(lsx_ctx* ctx, int32_t nmu, const double* mu, int32_t c
 
 /* Ng acceleration of the MALI loop, per column, opt-in: lsx_hip_ng.h, included below. */
 
+/* Emergent spectra at arbitrary wavelengths from what a context holds: lsx_hip_spectrum.h, included below. */
+
 /* GPU_MAX_HW_QUEUES=n for this process unless the caller has set it: call before the first HIP call. */
 int lsx_hip_request_hw_queues(int32_t n);
 
@@ -51,5 +53,6 @@ int lsx_hip_poison_lds(int32_t device, int32_t rounds);
 #include "lsx_hip_rates.h"
 #include "lsx_hip_depth.h"
 #include "lsx_hip_ng.h"
+#include "lsx_hip_spectrum.h"
 
 #endif /* LSX_HIP_H */

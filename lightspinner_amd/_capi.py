@@ -214,6 +214,13 @@ class LsxLibrary:
             d.lsx_hip_depth_rays.restype = C.c_int
             d.lsx_hip_depth_rays_work_cap.argtypes = [C.c_void_p, C.c_size_t]
             d.lsx_hip_depth_rays_work_cap.restype = C.c_int
+        self.has_spectrum = hasattr(d, 'lsx_hip_spectrum')             # include/lsx_hip_spectrum.h
+        if self.has_spectrum:
+            d.lsx_hip_spectrum.argtypes = [C.c_void_p, C.c_int32, _dp, _dp, _dp, _dp, _dp, C.c_int32, _dp, C.c_int32, C.c_int32,
+                                           _dp, C.c_size_t]
+            d.lsx_hip_spectrum.restype = C.c_int
+            d.lsx_hip_spectrum_work_cap.argtypes = [C.c_void_p, C.c_size_t]
+            d.lsx_hip_spectrum_work_cap.restype = C.c_int
         self.has_ng = hasattr(d, 'lsx_hip_ng_configure')               # include/lsx_hip_ng.h
         if self.has_ng:
             ip32 = C.POINTER(C.c_int32)

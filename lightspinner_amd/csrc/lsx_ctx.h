@@ -123,6 +123,12 @@ struct lsx_ctx : lsxd::LsxPlan {        // the plan (lsx_plan.h: dimensions, tab
     char* d_depth_ent = nullptr;
     double* d_depth_work = nullptr;
     size_t depth_work_doubles = 0, depth_work_cap = 0;      // cap 0: the default of include/lsx_hip_depth.h
+    // ... and of lsx_hip_spectrum (lsx_spectrum.hip): the tables of a call (they depend on the call's wavelengths: rebuilt per call,
+    // the buffer grows as needed) and the arrays of a pass (allocated at first use, under spec_work_cap bytes)
+    char* d_spec_tab = nullptr;
+    size_t spec_tab_bytes = 0;
+    double* d_spec_work = nullptr;
+    size_t spec_work_doubles = 0, spec_work_cap = 0;        // cap 0: the default of include/lsx_hip_spectrum.h
     // Ng acceleration of the populations (lsx_ng.hip, include/lsx_hip_ng.h): off (order 0) unless lsx_hip_ng_configure turns it on
     int ng_order = 0, ng_delay = 0;
     double* d_ng_hist = nullptr;         // [col][order + 2][NLtot][k]: the stored populations, slot = the column's counter

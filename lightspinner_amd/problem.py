@@ -460,6 +460,34 @@ class Engine:
         self.lib.check(self.lib.dll.lsx_hip_emergent_rays(self._h, mu.shape[0], _ptr(mu), int(col0), ncol, _ptr(out), out.nbytes))
         return out
 
+    def emergent_spectrum(self, mus, wavelength, alpha=None, bg_chi=None, bg_eta=None, bg_sca=None, col0=0, ncol=None,
+                          work_cap_bytes=None):
+        """Emergent intensity at arbitrary WAVELENGTHS (nm, strictly ascending; they need not be points of the problem's grid) and
+        viewing angles from what the engine holds (include/lsx_hip_spectrum.h, lsx_hip_spectrum), for columns [col0, col0 + ncol),
+        from the current populations and J.  alpha: [Ncont][nla], every continuum's cross-section at `wavelength` (continua in
+        table order; None only without continua).  bg_chi, bg_eta (and bg_sca in a sca_per_lambda problem): [ncol][nla][Nspace],
+        the background at `wavelength`; all None: the engine's own background is interpolated between its grid points (an
+        approximation between them).  J is interpolated likewise, always.
+        work_cap_bytes: the cap of the pass's device memory from this call on (None: unchanged; 0: the default).
+        Read-only.  -> [ncol][nla][nmu].  Only the HIP library computes it; there is no host version."""
+        if not getattr(self.lib, 'has_spectrum', False):
+            raise NotImplementedError('%s (%s) does not export lsx_hip_spectrum: emergent spectra at arbitrary wavelengths are '
+                                      'computed by the HIP library only' % (self.lib.path, self.lib.backend))
+        if work_cap_bytes is not None:
+            self.lib.check(self.lib.dll.lsx_hip_spectrum_work_cap(self._h, int(work_cap_bytes)))
+        mu = f64(np.atleast_1d(np.asarray(mus, dtype=np.float64)).reshape(-1))
+        w = f64(np.atleast_1d(np.asarray(wavelength, dtype=np.float64)).reshape(-1))
+        nla = w.shape[0]
+        ncol = self.ncol - int(col0) if ncol is None else int(ncol)
+        Ncont = self.problem.Ntrans - self.problem.Nlines
+        al = None if alpha is None else f64(alpha, (Ncont, nla))
+        bg = [None if a is None else f64(a, (max(ncol, 0), nla, self.problem.Nspace)) for a in (bg_chi, bg_eta, bg_sca)]
+        out = np.empty((max(ncol, 0), nla, mu.shape[0]), dtype=np.float64)
+        opt = lambda a: None if a is None else _ptr(a)
+        self.lib.check(self.lib.dll.lsx_hip_spectrum(self._h, nla, _ptr(w), opt(al), opt(bg[0]), opt(bg[1]), opt(bg[2]), mu.shape[0],
+                                                     _ptr(mu), int(col0), ncol, _ptr(out), out.nbytes))
+        return out
+
     def radiative_rates(self, col0=0, ncol=None, work_cap_bytes=None):
         """Radiative rates of every transition from what the engine holds (include/lsx_hip_rates.h, lsx_hip_radiative_rates): one
         formal solution over the engine's own rays from the current populations and J, for columns [col0, col0 + ncol).

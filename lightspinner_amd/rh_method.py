@@ -56,6 +56,7 @@ import numpy as np
 from . import _capi, atomdata
 from . import constants as Const
 from .problem import Problem, Transition, ColumnBlock, Engine, RadiativeRates, DepthRays
+from .spectrum import continuum_alpha
 
 _KNOWN_COLLISIONS = ('Omega', 'CI', 'CE')
 
@@ -437,14 +438,36 @@ class Context:
         self._results_changed(('J', 'I', 'Gamma'))
         return dJ
 
-    def compute_rays(self, mus=1.0):
+    def compute_rays(self, mus=1.0, wavelengths=None, background=None):
         """Emergent intensity at arbitrary viewing angles: what the reference computes with a Context on atmos.rays(mus)
         (atmosphere.py:386-393) that holds these populations and this J, after one formal_sol_gamma_matrices().  A float
-        gives [Nspect], a sequence [Nspect][nmu].  Nothing of the context changes: ctx.I stays the quadrature's."""
+        gives [Nspect], a sequence [Nspect][nmu].  Nothing of the context changes: ctx.I stays the quadrature's.
+        wavelengths: None for the context's own grid; otherwise any strictly ascending wavelengths [nm] -- an instrument's sampling of
+        a line, a finer grid, continuum points outside the grid: what the reference computes on
+        compute_wavelength_grid(extraWavelengths=wavelengths) with these populations (include/lsx_hip_spectrum.h); J is interpolated
+        linearly between the grid's points and held constant outside.  -> [nla] or [nla][nmu].
+        background: with `wavelengths`, an object with .chi, .eta (and .sca) of [nla][Nspace] at those wavelengths, e.g. the
+        reference's Background(atmos, SimpleNamespace(wavelength=wavelengths)); None: the context's own background is interpolated
+        like J, an approximation between grid points."""
         self._cancel_lookahead()                  # (the library's J is the last accepted call's again)
         self._push_host_edits()
         scalar = np.ndim(mus) == 0
-        out = self._engine.emergent_rays(np.atleast_1d(np.asarray(mus, dtype=np.float64)))[0]
+        mu = np.atleast_1d(np.asarray(mus, dtype=np.float64))
+        if wavelengths is None:
+            if background is not None:
+                raise ValueError('compute_rays: a background is taken with wavelengths only')
+            out = self._engine.emergent_rays(mu)[0]
+            return out[:, 0] if scalar else out
+        w = np.atleast_1d(np.asarray(wavelengths, dtype=np.float64)).reshape(-1)
+        conts = [t for a in self.activeAtoms for t in a.trans if not t.isLine]
+        alpha = (np.stack([np.asarray(continuum_alpha(t.transModel, w, lib=self._engine.lib), dtype=np.float64) for t in conts])
+                 if conts else None)
+        bg = {}
+        if background is not None:
+            bg = dict(bg_chi=np.asarray(background.chi, dtype=np.float64)[None], bg_eta=np.asarray(background.eta, dtype=np.float64)[None])
+            if self.problem.sca_per_lambda:
+                bg['bg_sca'] = np.asarray(background.sca, dtype=np.float64)[None]
+        out = self._engine.emergent_spectrum(mu, w, alpha=alpha, **bg)[0]
         return out[:, 0] if scalar else out
 
     def compute_depth_rays(self, mus=1.0, la0=0, nla=None, transition=None):
