@@ -16,6 +16,7 @@ import pytest
 import rays_cases as rc
 import spectrum_cases as sc
 from conftest import golden
+from final_pass_cases import given_background, made_up_profiles, made_up_wanted
 from helpers import build_data_fakes, restore_local_grids
 from lightspinner_amd import _capi, fixtures, synth
 from lightspinner_amd.problem import Engine
@@ -113,15 +114,6 @@ def wanted(prob, nwin=120):
     return w
 
 
-def given_background(prob, block, w):
-    """a background of the caller's that is NOT the interpolated one: the rule's values times a smooth factor"""
-    f = 1.0 + 0.01 * np.sin(np.arange(w.shape[0]))[:, None]
-    out = [sc.interp_rule(prob.wavelength, block.bg_chi, w) * f, sc.interp_rule(prob.wavelength, block.bg_eta, w) * f]
-    if prob.sca_per_lambda:
-        out.append(sc.interp_rule(prob.wavelength, block.bg_sca, w) * f)
-    return tuple(out)
-
-
 @pytest.mark.parametrize('fixture,solver', [('falc_ca.npz', 'linear'), ('falc_cah.npz', 'linear'), ('falc_ca.npz', 'parabolic')])
 def test_batches_after_mali_iterations(hip_lib, oracle_lib, fixture, solver):
     ncol = 7
@@ -203,20 +195,6 @@ def test_on_the_own_grid(hip_lib, oracle_lib):
 
 
 # ---- 5. depth limits, scattering per wavelength --------------------------------------------------------------------------------------
-def made_up_profiles(prob, block):
-    """profile inputs for the made-up problems of tests/toy.py (their lines are tens of nm wide)"""
-    depth = np.linspace(0.0, 1.0, prob.Nspace)
-    aD = np.tile(0.02 * (1.0 + depth), (block.ncol, prob.Nlines, 1))
-    vB = np.tile(6.0e6 * (1.0 + 0.5 * depth), (block.ncol, prob.Natoms, 1))
-    vl = 2.0e5 * np.sin(3.0 * depth[None, :] + np.arange(block.ncol)[:, None])
-    return aD, vB, vl
-
-
-def made_up_wanted(prob):
-    lam = prob.wavelength
-    return np.unique(np.concatenate([0.5 * (lam[1:] + lam[:-1])[::4], lam[::37], [0.8 * lam[0], 1.2 * lam[-1]]]))
-
-
 @pytest.mark.parametrize('solver', ['linear', 'parabolic'])
 def test_three_depths(hip_lib, oracle_lib, solver):
     """the smallest atmosphere lsx_create admits: the boundary value, one ordinary step (none under the parabolic rule) and the end point"""
