@@ -49,7 +49,9 @@ enum {
                             (tests/test_stat_equil_systems.py)                                   */
     /* 4 is unused: non-finite values are not an error, they propagate through dJ exactly as in
        the reference (numpy max, rh_method.py:705-706)                                            */
-    LSX_EUNSUPPORTED = 5 /* valid request this build cannot run (e.g. Nrays > 8)     */
+    LSX_EUNSUPPORTED = 5, /* valid request this build cannot run (e.g. Nrays > 8)     */
+    LSX_ENOCONV = 6      /* an iteration of the equation of state ended at its cap
+                            (lsx_hip_background.h); the message names the first (column, depth) */
 };
 
 /* One radiative transition as rh_method.ComputationalTransition sees it

@@ -18,8 +18,8 @@ LSX_SOLVER_LINEAR, LSX_SOLVER_PARABOLIC = 0, 1
 LSX_SWEEP_AUTO, LSX_SWEEP_RAY_PER_LANE, LSX_SWEEP_RAY_SERIAL = 0, 1, 2      # include/lsx.h: lsx_set_sweep_policy
 LSX_COLL_OMEGA, LSX_COLL_CI, LSX_COLL_CE = range(3)
 
-LSX_EINVAL, LSX_EDEVICE, LSX_ESINGULAR, LSX_EUNSUPPORTED = 1, 2, 3, 5
-ERRORS = {1: 'LSX_EINVAL', 2: 'LSX_EDEVICE', 3: 'LSX_ESINGULAR', 5: 'LSX_EUNSUPPORTED'}
+LSX_EINVAL, LSX_EDEVICE, LSX_ESINGULAR, LSX_EUNSUPPORTED, LSX_ENOCONV = 1, 2, 3, 5, 6
+ERRORS = {1: 'LSX_EINVAL', 2: 'LSX_EDEVICE', 3: 'LSX_ESINGULAR', 5: 'LSX_EUNSUPPORTED', 6: 'LSX_ENOCONV'}
 
 _dp = C.POINTER(C.c_double)
 
@@ -85,6 +85,11 @@ class LsxContinuumModel(C.Structure):
     _fields_ = [('hydrogenic', C.c_int32), ('n', C.c_int32), ('wavelength', _dp), ('alpha', _dp), ('lambdaEdge', C.c_double),
                 ('minLambda', C.c_double), ('alpha0', C.c_double), ('E_i', C.c_double), ('E_j', C.c_double),
                 ('stage_j', C.c_int32), ('reserved', C.c_int32)]
+
+
+class LsxEosTables(C.Structure):          # include/lsx_hip_background.h
+    _fields_ = [('npf', C.c_int32), ('nelem', C.c_int32), ('tpf', _dp), ('nstage', C.POINTER(C.c_int32)), ('pf', _dp), ('eion', _dp),
+                ('abund', _dp), ('amass', _dp), ('weight_per_H', C.c_double), ('iter_cap', C.c_int32), ('reserved', C.c_int32)]
 
 
 # every symbol include/lsx.h declares
@@ -221,6 +226,14 @@ class LsxLibrary:
             d.lsx_hip_spectrum.restype = C.c_int
             d.lsx_hip_spectrum_work_cap.argtypes = [C.c_void_p, C.c_size_t]
             d.lsx_hip_spectrum_work_cap.restype = C.c_int
+        self.has_background = hasattr(d, 'lsx_hip_background')         # include/lsx_hip_background.h
+        if self.has_background:
+            ip32 = C.POINTER(C.c_int32)
+            d.lsx_hip_eos.argtypes = [C.c_void_p, C.POINTER(LsxEosTables), C.c_int32, _dp, _dp, _dp, _dp, _dp, ip32]
+            d.lsx_hip_eos.restype = C.c_int
+            d.lsx_hip_background.argtypes = [C.c_void_p, C.POINTER(LsxEosTables), C.c_int32, C.c_int32, _dp, _dp, _dp, C.c_int32, _dp,
+                                             _dp, _dp, _dp, C.c_int32]
+            d.lsx_hip_background.restype = C.c_int
         self.has_ng = hasattr(d, 'lsx_hip_ng_configure')               # include/lsx_hip_ng.h
         if self.has_ng:
             ip32 = C.POINTER(C.c_int32)

@@ -1,0 +1,255 @@
+// lsx_background.hip -- the background of a column on the device (include/lsx_hip_background.h): the Wittmann equation of state
+// and the ATLAS-style continuous opacity of the reference's Background(atmos, spect) (background.py:15-53, witt.py).  gfx950.
+//   k_eos                 one thread per (column, depth): pgas, pe, the 17 partials, the count of pe_pg evaluations.  The waves
+//                         diverge on the iteration counts; that is accepted (about a hundred passes per point, once per column).
+//   k_bg_wave             one thread per wavelength: everything that depends on the wavelength alone (OpWave), so that the
+//                         opacity kernel reads it through wave-uniform (scalar) loads and its edge branches are wave-uniform
+//   k_background_opacity  one lane per flattened (column, depth) pair, a chunk of wavelengths per blockIdx.y: the temperature-
+//                         and partial-only terms once per lane in registers, then chi and eta to [col][la][k]
+// The formulas are lsx_background_dev.h; this unit is built with -ffp-contract=off.
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "../../include/lsx_hip.h"
+#include "../../include/lsx_hip_background.h"
+#include "lsx_background_prep.h"
+#include "lsx_ctx.h"
+
+using namespace lsxd;
+using namespace lsxbg;
+
+namespace {
+
+__global__ __launch_bounds__(64) void k_eos(EosParams P, long npts, const double* __restrict__ T, const double* __restrict__ nH,
+                                            double* __restrict__ pgas, double* __restrict__ pe, double* __restrict__ partials,
+                                            int32_t* __restrict__ status)
+{
+    const long i = (long)blockIdx.x * 64 + threadIdx.x;
+    if (i >= npts) return;
+    double pg, pel;
+    status[i] = eos_solve(P, T[i], nH[i], &pg, &pel, partials + i, (size_t)npts);      // partials: [17][npts]
+    pgas[i] = pg;
+    pe[i] = pel;
+}
+
+__global__ void k_bg_wave(const double* __restrict__ wavelength_nm, int nla, OpWave* __restrict__ W)
+{
+    const int l = blockIdx.x * blockDim.x + threadIdx.x;
+    if (l < nla) make_wave(wavelength_nm[l] * 10, &W[l]);
+}
+
+// points [p0, p0 + np) of the call (np = nb * Ns: whole columns) -> chi, eta [nb][nla][Ns]
+__global__ __launch_bounds__(64) void k_background_opacity(long p0, long np, long npts, int Ns, int nla, int la_chunk,
+                                                           const double* __restrict__ T, const double* __restrict__ pgas,
+                                                           const double* __restrict__ pe, const double* __restrict__ partials,
+                                                           const double* __restrict__ wavelength_nm, const OpWave* __restrict__ W,
+                                                           double* __restrict__ chi, double* __restrict__ eta)
+{
+    const long i = (long)blockIdx.x * 64 + threadIdx.x;
+    if (i >= np) return;
+    const long col = i / Ns;
+    const int k = (int)(i - col * Ns);
+    const long g = p0 + i;
+    const double t = T[g];
+    OpLane L;
+    make_lane(t, pgas[g], pe[g], partials + g, (size_t)npts, &L);
+    const int la0 = blockIdx.y * la_chunk, la1 = min(nla, la0 + la_chunk);
+    for (int la = la0; la < la1; ++la) {
+        const double x = cop_point(L, W[la]) / 1.0E-02;
+        const size_t o = ((size_t)col * nla + la) * Ns + k;
+        chi[o] = x;
+        eta[o] = planck_nm(t, wavelength_nm[la]) * x;
+    }
+}
+
+// sca = ne sigma_T: [nb][Ns], or broadcast over the wavelengths [nb][nla][Ns]
+__global__ void k_bg_sca(const double* __restrict__ ne, long np, int Ns, int nla, double sigma, double* __restrict__ sca)
+{
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= np) return;
+    const double v = ne[i] * sigma;
+    if (nla <= 0) { sca[i] = v; return; }
+    const long col = i / Ns;
+    const int k = (int)(i - col * Ns);
+    for (int la = 0; la < nla; ++la) sca[((size_t)col * nla + la) * Ns + k] = v;
+}
+
+struct DevBuf {      // device memory of one call, freed when the call returns
+    std::vector<void*> ptrs;
+    ~DevBuf() { for (void* p : ptrs) (void)hipFree(p); }
+    template <typename T>
+    int get(T** p, size_t count)
+    {
+        int rc = dmalloc(p, count);
+        if (!rc) ptrs.push_back(*p);
+        return rc;
+    }
+    template <typename T>
+    int put(T** p, const T* src, size_t count, hipStream_t st)
+    {
+        int rc = get(p, count);
+        if (rc) return rc;
+        HIPCHK(hipMemcpyAsync(*p, src, count * sizeof(T), hipMemcpyHostToDevice, st));
+        return LSX_OK;
+    }
+};
+
+struct EosOnDevice {
+    HostTables H;
+    EosParams P{};
+    double *T = nullptr, *nH = nullptr, *pgas = nullptr, *pe = nullptr, *partials = nullptr;
+    int32_t* status = nullptr;
+    std::vector<int32_t> h_status;
+};
+
+// checks + uploads + k_eos for npts = ncol * Ns points; on return the status is on the host (LSX_ENOCONV named, outputs valid)
+int run_eos(lsx_ctx* c, const char* who, const lsx_eos_tables* tab, long ncol, const double* temperature, const double* nHTot,
+            DevBuf& B, EosOnDevice& E)
+{
+    if (!c) return fail(LSX_EINVAL, "%s: null context", who);
+    const std::string bad = prepare_tables(tab, &E.H);
+    if (!bad.empty()) return fail(LSX_EINVAL, "%s: %s", who, bad.c_str());
+    if (ncol < 1 || !temperature || !nHTot) return fail(LSX_EINVAL, "%s: ncol < 1 or a null input array", who);
+    const int Ns = c->Nspace;
+    const size_t npts = (size_t)ncol * Ns;
+    long q;
+    if ((q = first_bad_positive(temperature, npts)) >= 0) return fail(LSX_EINVAL, "%s: temperature of column %ld, depth %ld is not finite and positive", who, q / Ns, q % Ns);
+    if ((q = first_bad_positive(nHTot, npts)) >= 0) return fail(LSX_EINVAL, "%s: nHTot of column %ld, depth %ld is not finite and positive", who, q / Ns, q % Ns);
+    HIPCHK(hipSetDevice(c->device));
+    int rc;
+#define TRY(x) do { rc = (x); if (rc) return rc; } while (0)
+    E.P = E.H.P;
+    double *d_tpf, *d_pf, *d_eion, *d_abund;
+    int32_t* d_nstage;
+    TRY(B.put(&d_tpf, tab->tpf, (size_t)tab->npf, c->stream));
+    TRY(B.put(&d_pf, tab->pf, (size_t)tab->nelem * 6 * tab->npf, c->stream));
+    TRY(B.put(&d_eion, tab->eion, (size_t)tab->nelem * 6, c->stream));
+    TRY(B.put(&d_nstage, tab->nstage, (size_t)tab->nelem, c->stream));
+    TRY(B.put(&d_abund, (const double*)E.H.abund.data(), (size_t)99, c->stream));
+    E.P.tpf = d_tpf; E.P.pf = d_pf; E.P.eion = d_eion; E.P.nstage = d_nstage; E.P.abund = d_abund;
+    TRY(B.put(&E.T, temperature, npts, c->stream));
+    TRY(B.put(&E.nH, nHTot, npts, c->stream));
+    TRY(B.get(&E.pgas, npts));
+    TRY(B.get(&E.pe, npts));
+    TRY(B.get(&E.partials, npts * NPART));
+    TRY(B.get(&E.status, npts));
+#undef TRY
+    hipLaunchKernelGGL(k_eos, dim3((unsigned)((npts + 63) / 64)), dim3(64), 0, c->stream, E.P, (long)npts, E.T, E.nH, E.pgas, E.pe,
+                       E.partials, E.status);
+    HIPCHK(hipGetLastError());
+    E.h_status.resize(npts);
+    HIPCHK(hipMemcpyAsync(E.h_status.data(), E.status, npts * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < npts; ++i)
+        if (E.h_status[i] < 0)
+            return fail(LSX_ENOCONV, "%s: the equation of state of column %zu, depth %zu ended at an iteration cap after %d pe_pg evaluations",
+                        who, i / Ns, i % Ns, -E.h_status[i]);
+    return LSX_OK;
+}
+
+} // namespace
+
+extern "C" int lsx_hip_eos(lsx_ctx* c, const lsx_eos_tables* tab, int32_t ncol, const double* temperature, const double* nHTot,
+                           double* pgas, double* pe, double* partials, int32_t* status)
+{
+    DevBuf B;
+    EosOnDevice E;
+    const int rc = run_eos(c, "lsx_hip_eos", tab, ncol, temperature, nHTot, B, E);
+    if (rc != LSX_OK && rc != LSX_ENOCONV) return rc;
+    const std::string msg = g_err;
+    const int Ns = c->Nspace;
+    const size_t npts = (size_t)ncol * Ns;
+    if (pgas) HIPCHK(hipMemcpy(pgas, E.pgas, npts * 8, hipMemcpyDeviceToHost));
+    if (pe) HIPCHK(hipMemcpy(pe, E.pe, npts * 8, hipMemcpyDeviceToHost));
+    if (partials) {       // device [17][col][k] -> [col][17][k]
+        std::vector<double> h(npts * NPART);
+        HIPCHK(hipMemcpy(h.data(), E.partials, npts * NPART * 8, hipMemcpyDeviceToHost));
+        for (size_t col = 0; col < (size_t)ncol; ++col)
+            for (int q = 0; q < NPART; ++q)
+                std::copy(h.begin() + q * npts + col * Ns, h.begin() + q * npts + (col + 1) * Ns, partials + (col * NPART + q) * Ns);
+    }
+    if (status) std::copy(E.h_status.begin(), E.h_status.end(), status);
+    if (rc) g_err = msg;
+    return rc;
+}
+
+extern "C" int lsx_hip_background(lsx_ctx* c, const lsx_eos_tables* tab, int32_t col0, int32_t ncol, const double* temperature,
+                                  const double* nHTot, const double* ne, int32_t nla, const double* wavelength, double* chi, double* eta,
+                                  double* sca, int32_t install)
+{
+    static const char* who = "lsx_hip_background";
+    if (!c) return fail(LSX_EINVAL, "%s: null context", who);
+    if (install != 0 && install != 1) return fail(LSX_EINVAL, "%s: install must be 0 or 1", who);
+    if (install && wavelength) return fail(LSX_EINVAL, "%s: install = 1 needs the context's own grid (wavelength == NULL)", who);
+    if (ncol < 1) return fail(LSX_EINVAL, "%s: ncol < 1", who);
+    if (install && (col0 < 0 || (long)col0 + ncol > c->ncol)) return fail(LSX_EINVAL, "%s: columns [%d, %d) outside the context's %d", who, col0, col0 + ncol, c->ncol);
+    if (wavelength) {
+        if (nla < 1) return fail(LSX_EINVAL, "%s: nla < 1", who);
+        for (int l = 0; l < nla; ++l)
+            if (!std::isfinite(wavelength[l]) || !(wavelength[l] > 0.0) || (l && !(wavelength[l] > wavelength[l - 1])))
+                return fail(LSX_EINVAL, "%s: wavelength[%d] is not finite, positive and above its predecessor", who, l);
+    } else {
+        nla = c->Nspect;
+    }
+    if (install)
+        for (int q = 0; q < ncol; ++q)
+            if (!c->cols_set[(size_t)col0 + q]) return fail(LSX_EINVAL, "%s: install into column %d, which lsx_set_columns has not set", who, col0 + q);
+    if (!temperature || !nHTot || !ne) return fail(LSX_EINVAL, "%s: a null input array", who);
+    const int Ns = c->Nspace;
+    const size_t npts = (size_t)ncol * Ns;
+    {
+        const double* arr[3] = {temperature, nHTot, ne};
+        const char* name[3] = {"temperature", "nHTot", "ne"};
+        for (int a = 0; a < 3; ++a) {
+            const long q = first_bad_positive(arr[a], npts);
+            if (q >= 0) return fail(LSX_EINVAL, "%s: %s of column %ld, depth %ld is not finite and positive", who, name[a], q / Ns, q % Ns);
+        }
+    }
+    DevBuf B;
+    EosOnDevice E;
+    int rc = run_eos(c, who, tab, ncol, temperature, nHTot, B, E);
+    if (rc) return rc;          // LSX_ENOCONV: nothing is installed
+#define TRY(x) do { rc = (x); if (rc) return rc; } while (0)
+    double *d_ne, *d_wl = c->d_wavelength;
+    OpWave* d_wave;
+    TRY(B.put(&d_ne, ne, npts, c->stream));
+    if (wavelength) TRY(B.put(&d_wl, wavelength, (size_t)nla, c->stream));
+    TRY(B.get(&d_wave, (size_t)nla));
+    hipLaunchKernelGGL(k_bg_wave, dim3((unsigned)((nla + 63) / 64)), dim3(64), 0, c->stream, d_wl, (int)nla, d_wave);
+    HIPCHK(hipGetLastError());
+
+    // columns in sub-chunks under lsx_set_columns' staging limit (chi and eta side by side, sigma behind them where it is per wavelength)
+    const bool sca_l = install && c->sca_per_lambda;
+    const size_t per_col = (size_t)nla * Ns;
+    const size_t chunk = std::max<size_t>(1, std::min<size_t>((size_t)ncol, ((size_t)32 << 20) / ((sca_l ? 3 : 2) * per_col)));
+    TRY(ensure_stage(c, (sca_l ? 3 : 2) * chunk * per_col + chunk * Ns));
+    const double sigma = thomson_sigma();
+    for (size_t b0 = 0; b0 < (size_t)ncol; b0 += chunk) {
+        const size_t nb = std::min(chunk, (size_t)ncol - b0);
+        const long np = (long)(nb * Ns);
+        double *s_chi = c->d_stage, *s_eta = s_chi + chunk * per_col, *s_sca = s_eta + chunk * per_col;
+        const int la_chunk = np >= 65536 ? 64 : 16;
+        hipLaunchKernelGGL(k_background_opacity, dim3((unsigned)((np + 63) / 64), (unsigned)((nla + la_chunk - 1) / la_chunk)), dim3(64), 0,
+                           c->stream, (long)(b0 * Ns), np, (long)npts, Ns, (int)nla, la_chunk, E.T, E.pgas, E.pe, E.partials, d_wl, d_wave, s_chi,
+                           s_eta);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(k_bg_sca, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, c->stream, d_ne + b0 * Ns, np, Ns, sca_l ? (int)nla : 0,
+                           sigma, s_sca);
+        HIPCHK(hipGetLastError());
+        if (install) TRY(background_from_device(c, (size_t)col0 + b0, nb, s_chi, s_eta, s_sca));
+        if (chi) HIPCHK(hipMemcpyAsync(chi + b0 * per_col, s_chi, nb * per_col * 8, hipMemcpyDeviceToHost, c->stream));
+        if (eta) HIPCHK(hipMemcpyAsync(eta + b0 * per_col, s_eta, nb * per_col * 8, hipMemcpyDeviceToHost, c->stream));
+        if (sca) {
+            if (!sca_l) {
+                HIPCHK(hipMemcpyAsync(sca + b0 * Ns, s_sca, nb * Ns * 8, hipMemcpyDeviceToHost, c->stream));
+            } else {       // (the per-depth value: row 0 of every column's broadcast)
+                for (size_t q = 0; q < nb; ++q)
+                    HIPCHK(hipMemcpyAsync(sca + (b0 + q) * Ns, s_sca + q * per_col, (size_t)Ns * 8, hipMemcpyDeviceToHost, c->stream));
+            }
+        }
+        HIPCHK(hipStreamSynchronize(c->stream));      // the staging buffer is re-used by the next sub-chunk
+    }
+#undef TRY
+    return LSX_OK;
+}

@@ -77,6 +77,7 @@ struct lsx_ctx : lsxd::LsxPlan {        // the plan (lsx_plan.h: dimensions, tab
            *d_Gpart = nullptr, *d_dJpart = nullptr, *d_dJcol = nullptr, *d_dPcol = nullptr, *d_res = nullptr;
     unsigned long long* d_singular = nullptr;
     std::vector<uint8_t> phi_set;    // per column: line profiles have been handed over or built
+    std::vector<uint8_t> cols_set;   // per column: lsx_set_columns has run (geometry and temperature are there; lsx_hip_background)
     size_t n_phi_set = 0;
     int solver = 0;               // LSX_SOLVER_* (lsx_set_formal_solver)
     int sweep_policy = LSX_SWEEP_AUTO;   // lsx_set_sweep_policy: which wavefront mapping the formal solution runs ...
@@ -195,6 +196,9 @@ int upload(T** dptr, const std::vector<T>& v, hipStream_t st)
 
 int ensure_stage(lsx_ctx* c, size_t doubles);    // grow the context's staging buffer
 int rebuild_derived(lsx_ctx* c, size_t col0, size_t ncol);     // continuum g_ij tables + nStar ratios from (nStar, T)
+// the background of columns [col0, col0 + ncol) from DEVICE arrays in the layout lsx_set_columns takes from the host (chi, eta:
+// [ncol][Nspect][Nspace]; sca: [ncol][Nspace], or like chi where sca_per_lambda): lsx_set_columns' own steps behind its uploads
+int background_from_device(lsx_ctx* c, size_t col0, size_t ncol, const double* d_chi, const double* d_eta, const double* d_sca);
 int profiles_from_device(lsx_ctx* c, size_t col0, size_t ncol, const double* dA, const double* dV, const double* dL);
 void profiles_handed_over(lsx_ctx* c, size_t col0, size_t ncol);    // these columns' profiles no longer come from kept inputs
 void mark_profiles_set(lsx_ctx* c, size_t col0, size_t ncol);

@@ -1180,6 +1180,30 @@ int rebuild_derived(lsx_ctx* c, size_t cc, size_t nb)
     return LSX_OK;
 }
 
+// lsx_set_columns' steps for bg_chi / bg_eta / bg_sca with the natural layout already on the device (lsx_hip_background's install):
+// [la][k] -> tile-major through the same pack, the (chi, eta) pairs where the ray-serial instances read them, then what
+// lsx_set_columns rebuilds.  Enqueued on the context's stream.
+int background_from_device(lsx_ctx* c, size_t cc, size_t nb, const double* d_chi, const double* d_eta, const double* d_sca)
+{
+    c->optab_fresh = false;
+    c->spec_valid = false;
+    int rc;
+    if ((rc = launch_tiles_pack(c, d_chi, c->d_bgchi + cc * c->til_col, (int)nb, false))) return rc;
+    if ((rc = launch_tiles_pack(c, d_eta, c->d_bgeta + cc * c->til_col, (int)nb, false))) return rc;
+    if (c->d_bgce) {
+        const size_t n = nb * c->til_col;
+        hipLaunchKernelGGL(k_interleave2, dim3((unsigned)std::min<size_t>((n + 255) / 256, 65535)), dim3(256), 0, c->stream,
+                           c->d_bgchi + cc * c->til_col, c->d_bgeta + cc * c->til_col, c->d_bgce + 2 * cc * c->til_col, n);
+        HIPCHK(hipGetLastError());
+    }
+    if (c->sca_per_lambda) {
+        if ((rc = launch_tiles_pack(c, d_sca, c->d_sca + cc * c->sca_col, (int)nb, false))) return rc;
+    } else {
+        HIPCHK(hipMemcpyAsync(c->d_sca + cc * c->Nspace, d_sca, nb * c->Nspace * 8, hipMemcpyDeviceToDevice, c->stream));
+    }
+    return rebuild_derived(c, cc, nb);
+}
+
 // compute_phi (rh_method.py:198-243) for columns [cc, cc + nb) from DEVICE arrays dA [nb][Nlines][Ns], dV [nb][Natoms][Ns],
 // dL [nb][Ns] or null: the sweep's (tile, line) profile blocks and the normalisation wphi.  Enqueued on the context's stream.
 int profiles_from_device(lsx_ctx* c, size_t cc, size_t nb, const double* dA, const double* dV, const double* dL)
@@ -1547,6 +1571,7 @@ int lsx_create_with_options(const lsx_problem* d, int32_t ncol, int32_t device, 
     c->d_dPcol = c->d_res + nc;
     c->d_singular = reinterpret_cast<unsigned long long*>(c->d_res + 2 * nc);
     c->phi_set.assign(nc, 0);
+    c->cols_set.assign(nc, 0);
     TRY(dmalloc(&c->d_debug, 1024 * 16));
     if (c->any_cont) {          // the nStar ratio of every continuum (g_ij = ratio x E_T)
         TRY(upload(&c->d_cont_li, c->cont_li, c->stream));
@@ -1649,6 +1674,7 @@ int lsx_set_columns(lsx_ctx* c, int32_t col0, int32_t ncol, const lsx_columns* s
     }
 #undef TRY
     profiles_handed_over(c, o, (size_t)ncol);
+    for (int q = 0; q < ncol; ++q) c->cols_set[o + q] = 1;
     for (int q = 0; q < ncol; ++q) {       // profiles of these columns: handed over, or still to come (lsx_set_line_profiles)
         const uint8_t v = (have_phi || !c->Nlines) ? 1 : 0;
         c->n_phi_set += (size_t)v - c->phi_set[o + q];

@@ -532,6 +532,62 @@ class Engine:
                                                        int(np.prod(shape)) * 8, int(np.prod(shape[:2] + shape[3:])) * 8))
         return DepthRays(mu, la0, **out)
 
+    def _background_lib(self, entry):
+        if not getattr(self.lib, 'has_background', False):
+            raise NotImplementedError('%s (%s) does not export %s: the equation of state and the background opacity are computed '
+                                      'by the HIP library only' % (self.lib.path, self.lib.backend, entry))
+
+    def eos(self, tables, temperature, nHTot):
+        """The Wittmann equation of state of the reference's Background (include/lsx_hip_background.h, lsx_hip_eos) for
+        temperature, nHTot [ncol][Nspace] (SI; a single column may be 1-D); `tables` is a background.EosTables.
+        -> background.EosResult with .pgas, .pe [ncol][Nspace] (dyn cm^-2), .partials [ncol][17][Nspace] and .status (the number of
+        witt.pe_pg evaluations per point).  A point that ends at an iteration cap raises LsxError (LSX_ENOCONV).  Does not touch
+        the engine's state; any ncol.  Only the HIP library computes it."""
+        from .background import EosResult
+        self._background_lib('lsx_hip_eos')
+        Ns = self.problem.Nspace
+        T = f64(np.asarray(temperature, dtype=np.float64).reshape(-1, Ns))
+        nH = f64(nHTot).reshape(-1, Ns)
+        if nH.shape != T.shape:
+            raise ValueError('temperature and nHTot differ in shape')
+        ncol = T.shape[0]
+        pgas, pe, part = np.empty((ncol, Ns)), np.empty((ncol, Ns)), np.empty((ncol, 17, Ns))
+        status = np.zeros((ncol, Ns), dtype=np.int32)
+        ctab, _keep = tables.to_c()
+        rc = self.lib.dll.lsx_hip_eos(self._h, C.byref(ctab), ncol, _ptr(T), _ptr(nH), _ptr(pgas), _ptr(pe), _ptr(part),
+                                      status.ctypes.data_as(C.POINTER(C.c_int32)))
+        res = EosResult(pgas, pe, part, status)
+        if rc == _capi.LSX_ENOCONV:
+            err = _capi.LsxError(rc, self.lib.dll.lsx_last_error().decode(errors='replace'))
+            err.result = res            # the outputs are written all the same: which points, and how far they got
+            raise err
+        self.lib.check(rc)
+        return res
+
+    def background(self, tables, temperature, nHTot, ne, wavelength=None, col0=0, install=False, read_back=True):
+        """Background opacity, emissivity and Thomson scattering coefficient of the reference's Background(atmos, spect)
+        (include/lsx_hip_background.h, lsx_hip_background) for temperature, nHTot, ne [ncol][Nspace] (SI; one column may be 1-D).
+        wavelength: nm, strictly ascending (None: the problem's own grid).  install=True (own grid only) puts the result into the
+        engine as the background of columns [col0, col0 + ncol), which set_columns must have set before.
+        -> (chi, eta, sca) with chi, eta [ncol][nla][Nspace] -- what emergent_spectrum takes as bg_chi / bg_eta -- and sca
+        [ncol][Nspace]; None when installing with read_back=False.  Only the HIP library computes it."""
+        self._background_lib('lsx_hip_background')
+        Ns = self.problem.Nspace
+        T = f64(np.asarray(temperature, dtype=np.float64).reshape(-1, Ns))
+        nH, el = f64(nHTot).reshape(-1, Ns), f64(ne).reshape(-1, Ns)
+        if nH.shape != T.shape or el.shape != T.shape:
+            raise ValueError('temperature, nHTot and ne differ in shape')
+        ncol = T.shape[0]
+        w = None if wavelength is None else f64(np.atleast_1d(np.asarray(wavelength, dtype=np.float64)).reshape(-1))
+        nla = self.problem.Nspect if w is None else w.shape[0]
+        want = read_back or not install
+        chi, eta, sca = (np.empty((ncol, nla, Ns)), np.empty((ncol, nla, Ns)), np.empty((ncol, Ns))) if want else (None, None, None)
+        opt = lambda a: None if a is None else _ptr(a)
+        ctab, _keep = tables.to_c()
+        self.lib.check(self.lib.dll.lsx_hip_background(self._h, C.byref(ctab), int(col0), ncol, _ptr(T), _ptr(nH), _ptr(el), nla, opt(w),
+                                                       opt(chi), opt(eta), opt(sca), 1 if install else 0))
+        return (chi, eta, sca) if want else None
+
     def configure_ng(self, order=2, delay=0):
         """Ng acceleration of the populations behind every stat_equil of this engine (include/lsx_hip_ng.h, lsx_hip_ng_configure):
         order 1 or 2, 0 switches it off; `delay` statistical equilibria pass before the first vector is stored.  Also takes an
