@@ -43,6 +43,9 @@ int lsx_hip_emergent_rays(lsx_ctx* ctx, int32_t nmu, const double* mu, int32_t c
 /* The background of a column on the device -- the Wittmann equation of state and the continuous opacity of the reference's
  * Background(atmos, spect): lsx_hip_background.h, included below. */
 
+/* Depth-scale conversion on the device -- column mass, height and tau500 from any one of them, the reference's
+ * AtmosphereConstructor.convert_scales: lsx_hip_scales.h, included below. */
+
 /* GPU_MAX_HW_QUEUES=n for this process unless the caller has set it: call before the first HIP call. */
 int lsx_hip_request_hw_queues(int32_t n);
 
@@ -58,5 +61,6 @@ int lsx_hip_poison_lds(int32_t device, int32_t rounds);
 #include "lsx_hip_ng.h"
 #include "lsx_hip_spectrum.h"
 #include "lsx_hip_background.h"
+#include "lsx_hip_scales.h"
 
 #endif /* LSX_HIP_H */

@@ -87,6 +87,9 @@ class LsxContinuumModel(C.Structure):
                 ('stage_j', C.c_int32), ('reserved', C.c_int32)]
 
 
+LSX_SCALE_GEOMETRIC, LSX_SCALE_COLUMN_MASS, LSX_SCALE_TAU500 = 0, 1, 2      # include/lsx_hip_scales.h
+
+
 class LsxEosTables(C.Structure):          # include/lsx_hip_background.h
     _fields_ = [('npf', C.c_int32), ('nelem', C.c_int32), ('tpf', _dp), ('nstage', C.POINTER(C.c_int32)), ('pf', _dp), ('eion', _dp),
                 ('abund', _dp), ('amass', _dp), ('weight_per_H', C.c_double), ('iter_cap', C.c_int32), ('reserved', C.c_int32)]
@@ -234,6 +237,11 @@ class LsxLibrary:
             d.lsx_hip_background.argtypes = [C.c_void_p, C.POINTER(LsxEosTables), C.c_int32, C.c_int32, _dp, _dp, _dp, C.c_int32, _dp,
                                              _dp, _dp, _dp, C.c_int32]
             d.lsx_hip_background.restype = C.c_int
+        self.has_scales = hasattr(d, 'lsx_hip_convert_scales')         # include/lsx_hip_scales.h
+        if self.has_scales:
+            d.lsx_hip_convert_scales.argtypes = [C.c_void_p, C.POINTER(LsxEosTables), C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp,
+                                                 C.c_double, _dp, _dp, _dp, _dp, C.c_int32]
+            d.lsx_hip_convert_scales.restype = C.c_int
         self.has_ng = hasattr(d, 'lsx_hip_ng_configure')               # include/lsx_hip_ng.h
         if self.has_ng:
             ip32 = C.POINTER(C.c_int32)

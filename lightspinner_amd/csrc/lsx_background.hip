@@ -6,15 +6,21 @@
 //                         opacity kernel reads it through wave-uniform (scalar) loads and its edge branches are wave-uniform
 //   k_background_opacity  one lane per flattened (column, depth) pair, a chunk of wavelengths per blockIdx.y: the temperature-
 //                         and partial-only terms once per lane in registers, then chi and eta to [col][la][k]
-// The formulas are lsx_background_dev.h; this unit is built with -ffp-contract=off.
+//   k_depth_scales        the depth-scale conversion behind the two (include/lsx_hip_scales.h): one lane per column, the recurrence
+//                         of atmosphere.py:93-141 along depth with the running values in registers, the [col][k] arrays moved
+//                         through LDS in chunks of SC_KC depths so that global memory is touched in contiguous runs
+// The formulas are lsx_background_dev.h and lsx_scales_dev.h; this unit is built with -ffp-contract=off.
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
 #include "../../include/lsx_hip.h"
 #include "../../include/lsx_hip_background.h"
+#include "../../include/lsx_hip_scales.h"
 #include "lsx_background_prep.h"
 #include "lsx_ctx.h"
+#include "lsx_scales_dev.h"
+#include "lsx_scales_prep.h"
 
 using namespace lsxd;
 using namespace lsxbg;
@@ -73,6 +79,76 @@ __global__ void k_bg_sca(const double* __restrict__ ne, long np, int Ns, int nla
     const long col = i / Ns;
     const int k = (int)(i - col * Ns);
     for (int la = 0; la < nla; ++la) sca[((size_t)col * nla + la) * Ns + k] = v;
+}
+
+// Depth chunk of k_depth_scales' staging, and the padded row of a column in LDS (an odd count of 8-byte words: the 64 lanes, each
+// on its own row at the same depth, fall on different banks).  Three tiles of 64 x SC_ROW doubles: 25.5 KiB per workgroup.
+constexpr int SC_KC = 16, SC_ROW = SC_KC + 1;
+
+// columns [64 blockIdx.x, +64) of the call; chi: chi_c [ncol][Ns] from k_background_opacity at 500 nm.  height, cmass, tau may
+// be null.  The geometric scale's height is its input: it is not written.
+template <int SCALE>
+__global__ __launch_bounds__(64) void k_depth_scales(int ncol, int Ns, double amu_wph, double wph, double gravity,
+                                                     const double* __restrict__ ds, const double* __restrict__ T,
+                                                     const double* __restrict__ nH, const double* __restrict__ ne,
+                                                     const double* __restrict__ chi, double* __restrict__ height,
+                                                     double* __restrict__ cmass, double* __restrict__ tau)
+{
+    __shared__ double s_a[64 * SC_ROW], s_b[64 * SC_ROW], s_c[64 * SC_ROW];      // in: depth scale, nHTot, chi_c; out: height, cmass, tau
+    __shared__ double s_h1[64];
+    const int lane = threadIdx.x;
+    const long c0 = (long)blockIdx.x * 64;
+    const int nc = (int)min((long)64, (long)ncol - c0);
+    const size_t base = (size_t)c0 * Ns;
+    lsxsc::Run R{};
+    for (int k0 = 0; k0 < Ns; k0 += SC_KC) {
+        const int kc = min(SC_KC, Ns - k0);
+        for (int i = lane; i < 64 * SC_KC; i += 64) {          // 16 consecutive lanes read 16 consecutive depths of a column
+            const int col = i / SC_KC, kk = i % SC_KC;
+            if (col < nc && kk < kc) {
+                const size_t g = base + (size_t)col * Ns + k0 + kk;
+                s_a[col * SC_ROW + kk] = ds[g];
+                s_b[col * SC_ROW + kk] = nH[g];
+                s_c[col * SC_ROW + kk] = chi[g];
+            }
+        }
+        __syncthreads();
+        if (lane < nc) {
+            double* a = s_a + lane * SC_ROW;
+            double* b = s_b + lane * SC_ROW;
+            double* x = s_c + lane * SC_ROW;
+            for (int kk = 0; kk < kc; ++kk) {
+                const double rho = lsxsc::rho_si(amu_wph, b[kk]);
+                if (k0 + kk == 0) {
+                    const size_t g0 = base + (size_t)lane * Ns;
+                    lsxsc::start<SCALE>(R, a[0], a[1], rho, x[0], SCALE == lsxsc::GEOMETRIC ? T[g0] : 0.0, b[0],
+                                        SCALE == lsxsc::GEOMETRIC ? ne[g0] : 0.0, wph, gravity);
+                } else {
+                    lsxsc::step<SCALE>(R, a[kk], rho, x[kk]);
+                }
+                a[kk] = R.height;
+                b[kk] = R.cmass;
+                x[kk] = R.tau;
+            }
+        }
+        __syncthreads();
+        for (int i = lane; i < 64 * SC_KC; i += 64) {
+            const int col = i / SC_KC, kk = i % SC_KC;
+            if (col < nc && kk < kc) {
+                const size_t g = base + (size_t)col * Ns + k0 + kk;
+                if (SCALE != lsxsc::GEOMETRIC && height) height[g] = s_a[col * SC_ROW + kk];
+                if (cmass) cmass[g] = s_b[col * SC_ROW + kk];
+                if (tau) tau[g] = s_c[col * SC_ROW + kk];
+            }
+        }
+        __syncthreads();
+    }
+    if (SCALE == lsxsc::GEOMETRIC || !height) return;
+    // second pass: height -= hTau1 (:105, :137), the workgroup's columns as one contiguous run
+    s_h1[lane] = lane < nc ? lsxsc::tau1_last(R.t1, R.height) : 0.0;
+    __syncthreads();
+    const long n = (long)nc * Ns;
+    for (long i = lane; i < n; i += 64) height[base + i] -= s_h1[i / Ns];
 }
 
 struct DevBuf {      // device memory of one call, freed when the call returns
@@ -250,6 +326,76 @@ extern "C" int lsx_hip_background(lsx_ctx* c, const lsx_eos_tables* tab, int32_t
         }
         HIPCHK(hipStreamSynchronize(c->stream));      // the staging buffer is re-used by the next sub-chunk
     }
+#undef TRY
+    return LSX_OK;
+}
+
+extern "C" int lsx_hip_convert_scales(lsx_ctx* c, const lsx_eos_tables* tab, int32_t scale, int32_t col0, int32_t ncol,
+                                      const double* depth_scale, const double* temperature, const double* nHTot, const double* ne,
+                                      double gravity, double* height, double* cmass, double* tau_ref, double* chi_ref, int32_t install)
+{
+    static const char* who = "lsx_hip_convert_scales";
+    if (!c) return fail(LSX_EINVAL, "%s: null context", who);
+    if (install != 0 && install != 1) return fail(LSX_EINVAL, "%s: install must be 0 or 1", who);
+    const int Ns = c->Nspace;
+    {
+        const std::string bad = lsxsc::check_arrays(scale, ncol, Ns, depth_scale, temperature, nHTot, ne, gravity);
+        if (!bad.empty()) return fail(LSX_EINVAL, "%s: %s", who, bad.c_str());
+    }
+    if (install) {
+        if (col0 < 0 || (long)col0 + ncol > c->ncol) return fail(LSX_EINVAL, "%s: columns [%d, %d) outside the context's %d", who, col0, col0 + ncol, c->ncol);
+        for (int q = 0; q < ncol; ++q)
+            if (!c->cols_set[(size_t)col0 + q]) return fail(LSX_EINVAL, "%s: install into column %d, which lsx_set_columns has not set", who, col0 + q);
+    }
+    const bool geo = scale == LSX_SCALE_GEOMETRIC;
+    const size_t npts = (size_t)ncol * Ns;
+    DevBuf B;
+    EosOnDevice E;
+    int rc = run_eos(c, who, tab, ncol, temperature, nHTot, B, E);
+    if (rc) return rc;          // LSX_ENOCONV: nothing is installed, nothing is written
+#define TRY(x) do { rc = (x); if (rc) return rc; } while (0)
+    // chi_c: the opacity path with one wavelength, 500.0 nm (witt.contOpacity(..., [5000.0]), atmosphere.py:91)
+    const double w500 = 500.0;
+    double *d_wl, *d_chi, *d_eta, *d_ds, *d_ne = nullptr, *d_h = nullptr, *d_cm = nullptr, *d_tau = nullptr;
+    OpWave* d_wave;
+    TRY(B.put(&d_wl, &w500, (size_t)1, c->stream));
+    TRY(B.get(&d_wave, (size_t)1));
+    TRY(B.get(&d_chi, npts));
+    TRY(B.get(&d_eta, npts));
+    TRY(B.put(&d_ds, depth_scale, npts, c->stream));
+    if (geo) TRY(B.put(&d_ne, ne, npts, c->stream));
+    if (!geo && (height || install)) TRY(B.get(&d_h, npts));
+    if (cmass) TRY(B.get(&d_cm, npts));
+    if (tau_ref) TRY(B.get(&d_tau, npts));
+    hipLaunchKernelGGL(k_bg_wave, dim3(1), dim3(64), 0, c->stream, d_wl, 1, d_wave);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_background_opacity, dim3((unsigned)((npts + 63) / 64), 1), dim3(64), 0, c->stream, 0L, (long)npts, (long)npts, Ns, 1, 16,
+                       E.T, E.pgas, E.pe, E.partials, d_wl, d_wave, d_chi, d_eta);
+    HIPCHK(hipGetLastError());
+    if (d_h || d_cm || d_tau) {
+        const dim3 grid((unsigned)((ncol + 63) / 64));
+        const double wph = tab->weight_per_H;
+#define SC_LAUNCH(S) hipLaunchKernelGGL(k_depth_scales<S>, grid, dim3(64), 0, c->stream, (int)ncol, Ns, E.P.rho_unit, wph, gravity, d_ds, E.T, \
+                                        E.nH, d_ne, d_chi, d_h, d_cm, d_tau)
+        if (scale == LSX_SCALE_COLUMN_MASS) SC_LAUNCH(lsxsc::COLUMN_MASS);
+        else if (geo) SC_LAUNCH(lsxsc::GEOMETRIC);
+        else SC_LAUNCH(lsxsc::TAU500);
+#undef SC_LAUNCH
+        HIPCHK(hipGetLastError());
+    }
+    if (install) {      // what lsx_set_columns invalidates for a new height: the operand table of the ray-serial sweeps, a discardable formal solution
+        c->optab_fresh = false;
+        c->spec_valid = false;
+        HIPCHK(hipMemcpyAsync(c->d_height + (size_t)col0 * Ns, geo ? d_ds : d_h, npts * 8, hipMemcpyDeviceToDevice, c->stream));
+    }
+    if (height) {
+        if (geo) std::copy(depth_scale, depth_scale + npts, height);       // the input, bit for bit
+        else HIPCHK(hipMemcpyAsync(height, d_h, npts * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    if (cmass) HIPCHK(hipMemcpyAsync(cmass, d_cm, npts * 8, hipMemcpyDeviceToHost, c->stream));
+    if (tau_ref) HIPCHK(hipMemcpyAsync(tau_ref, d_tau, npts * 8, hipMemcpyDeviceToHost, c->stream));
+    if (chi_ref) HIPCHK(hipMemcpyAsync(chi_ref, d_chi, npts * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
 #undef TRY
     return LSX_OK;
 }

@@ -1360,6 +1360,7 @@ int lsx_create_with_options(const lsx_problem* d, int32_t ncol, int32_t device, 
         const int orc = options_apply(options, &copt, &oerr);
         if (orc) return fail(orc, "lsx_create_with_options: %s", oerr.c_str());
     }
+    copt.plan.min_depths = 2;       // two depths make a depth scale (lsx_hip_convert_scales); enqueue_fs asks for three
     const PlanOptions& opt = copt.plan;
     LsxPlan plan;
     {
@@ -1718,6 +1719,7 @@ static void launch_build_optab(lsx_ctx* c)
 
 static int enqueue_fs(lsx_ctx* c, bool timed, bool speculative = false)
 {
+    if (c->Nspace < 3) return fail(LSX_EUNSUPPORTED, "formal_sol_gamma: needs Nspace >= 3 (formal_solver.py:120-139)");
     if (c->n_phi_set != (size_t)c->ncol) {
         size_t q = 0;
         while (q < (size_t)c->ncol && c->phi_set[q]) ++q;

@@ -51,7 +51,9 @@ int plan_build(const lsx_problem* d, const PlanOptions& opt, LsxPlan* out, std::
 {
     if (!d || !out) return perr(err, LSX_EINVAL, "lsx_create: null argument");
     if (d->abi_version != LSX_ABI_VERSION) return perr(err, LSX_EINVAL, "lsx_create: ABI version mismatch");
-    if (d->Nspace < 3) return perr(err, LSX_EINVAL, "lsx_create: Nspace must be >= 3 (formal_solver.py:120-139)");
+    if (d->Nspace < opt.min_depths)
+        return perr(err, LSX_EINVAL, opt.min_depths >= 3 ? "lsx_create: Nspace must be >= 3 (formal_solver.py:120-139)"
+                                                         : "lsx_create: Nspace must be >= 2 (>= 3 for a formal solution, formal_solver.py:120-139)");
     if (d->Nrays < 1 || d->Nspect < 1 || d->Natoms < 1 || d->Ntrans < 0) return perr(err, LSX_EINVAL, "lsx_create: bad dimensions");
     if (d->Nrays > LSX_WAVE) return perr(err, LSX_EUNSUPPORTED, "lsx_create: Nrays > 64 is not supported by this build");
     if (d->Natoms > LSX_MAX_ATOMS) return perr(err, LSX_EUNSUPPORTED, "lsx_create: more than %d active atoms", LSX_MAX_ATOMS);

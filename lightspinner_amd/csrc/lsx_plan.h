@@ -255,6 +255,8 @@ struct PlanOptions {           // diagnostic switches (lsx_create reads them fro
                                // integrands itself).  OFF by default: built, parity-green on every GPU test, and measured 2 % SLOWER than the
                                // epilogue kernel it replaces (profiles/r05/ab_epilogue_in_sweep.txt; DESIGN.md 4.2 says what it would take)
     bool no_fold = false;      // fold=0 / LSX_NO_FOLD: the ray-serial classes keep the pre-pass and the effective-background streams (round 4)
+    int min_depths = 3;        // fewest depths a plan is made for: a sweep needs three (formal_solver.py:120-139).  lsx_create asks for two: a context
+                               // of two depths carries the depth-scale conversion (lsx_hip_convert_scales); its formal solution refuses it
     int rs_max_npt = 2;        // LSX_RS_MAX_NPT: classes with more per-ray slots keep one ray per lane (diagnostic: 1 leaves the two-slot tiles to lsx_sweep.hip)
 };
 

@@ -415,6 +415,7 @@ extern "C" int lsx_hip_radiative_rates(lsx_ctx* c, int32_t col0, int32_t ncol, d
     // ---- everything is checked on the host before anything is launched ----
     if (!c) return fail(LSX_EINVAL, "lsx_hip_radiative_rates: null context");
     if (!Rij && !Rji && !Rji_ref) return fail(LSX_EINVAL, "lsx_hip_radiative_rates: all three outputs are NULL");
+    if (c->Nspace < 3) return fail(LSX_EUNSUPPORTED, "lsx_hip_radiative_rates: needs Nspace >= 3");
     if (col0 < 0 || ncol < 1 || (int64_t)col0 + ncol > c->ncol)
         return fail(LSX_EINVAL, "lsx_hip_radiative_rates: columns [%d, %d) are outside the context's %d", (int)col0, (int)col0 + (int)ncol, c->ncol);
     const size_t per = (size_t)c->Ntrans * c->Nspace;

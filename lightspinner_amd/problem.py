@@ -588,6 +588,37 @@ class Engine:
                                                        opt(chi), opt(eta), opt(sca), 1 if install else 0))
         return (chi, eta, sca) if want else None
 
+    def convert_scales(self, tables, scale, depth_scale, temperature, nHTot, ne=None, logG=2.44, col0=0, install=False, read_back=True):
+        """Column mass, geometric height and tau500 of columns given on one of the three, the reference's
+        AtmosphereConstructor.convert_scales (include/lsx_hip_scales.h, lsx_hip_convert_scales).  scale: 'geometric',
+        'column_mass', 'tau500' or the LSX_SCALE_* values; depth_scale, temperature, nHTot [ncol][Nspace] (SI; one column may be
+        1-D); ne likewise, needed for the geometric scale only, as is logG.  install=True puts the resulting height into the engine
+        as the height of columns [col0, col0 + ncol), which set_columns must have set before.
+        -> atmosphere.Scales with .height, .cmass, .tau_ref, .chi_ref [ncol][Nspace] (chi_ref: the continuous opacity at 500 nm,
+        m^-1); None when installing with read_back=False.  Only the HIP library computes it."""
+        from .atmosphere import Scales, scale_code
+        if not getattr(self.lib, 'has_scales', False):
+            raise NotImplementedError('%s (%s) does not export lsx_hip_convert_scales: the depth scales are converted by the HIP '
+                                      'library only' % (self.lib.path, self.lib.backend))
+        code = scale_code(scale)
+        Ns = self.problem.Nspace
+        ds = f64(np.asarray(depth_scale, dtype=np.float64).reshape(-1, Ns))
+        T, nH = f64(temperature).reshape(-1, Ns), f64(nHTot).reshape(-1, Ns)
+        el = None if ne is None else f64(ne).reshape(-1, Ns)
+        if T.shape != ds.shape or nH.shape != ds.shape or (el is not None and el.shape != ds.shape):
+            raise ValueError('depth_scale, temperature, nHTot and ne differ in shape')
+        if code == _capi.LSX_SCALE_GEOMETRIC and el is None:
+            raise ValueError('the geometric scale needs ne')
+        ncol = ds.shape[0]
+        want = read_back or not install
+        out = [np.empty((ncol, Ns)) for _ in range(4)] if want else [None] * 4
+        opt = lambda a: None if a is None else _ptr(a)
+        ctab, _keep = tables.to_c()
+        self.lib.check(self.lib.dll.lsx_hip_convert_scales(self._h, C.byref(ctab), code, int(col0), ncol, _ptr(ds), _ptr(T), _ptr(nH), opt(el),
+                                                           10**logG, opt(out[0]), opt(out[1]), opt(out[2]), opt(out[3]),
+                                                           1 if install else 0))
+        return Scales(*out) if want else None
+
     def configure_ng(self, order=2, delay=0):
         """Ng acceleration of the populations behind every stat_equil of this engine (include/lsx_hip_ng.h, lsx_hip_ng_configure):
         order 1 or 2, 0 switches it off; `delay` statistical equilibria pass before the first vector is stored.  Also takes an
