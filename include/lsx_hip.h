@@ -46,6 +46,9 @@ int lsx_hip_emergent_rays(lsx_ctx* ctx, int32_t nmu, const double* mu, int32_t c
 /* Depth-scale conversion on the device -- column mass, height and tau500 from any one of them, the reference's
  * AtmosphereConstructor.convert_scales: lsx_hip_scales.h, included below. */
 
+/* LTE populations of any atoms, active in the context or not -- the reference's RadiativeSet.compute_eq_pops, which supplies
+ * lsx_set_atmosphere's nHGround and nTotal: lsx_hip_eqpops.h, included below. */
+
 /* GPU_MAX_HW_QUEUES=n for this process unless the caller has set it: call before the first HIP call. */
 int lsx_hip_request_hw_queues(int32_t n);
 
@@ -62,5 +65,6 @@ int lsx_hip_poison_lds(int32_t device, int32_t rounds);
 #include "lsx_hip_spectrum.h"
 #include "lsx_hip_background.h"
 #include "lsx_hip_scales.h"
+#include "lsx_hip_eqpops.h"
 
 #endif /* LSX_HIP_H */

@@ -95,6 +95,10 @@ class LsxEosTables(C.Structure):          # include/lsx_hip_background.h
                 ('abund', _dp), ('amass', _dp), ('weight_per_H', C.c_double), ('iter_cap', C.c_int32), ('reserved', C.c_int32)]
 
 
+class LsxEqAtom(C.Structure):            # include/lsx_hip_eqpops.h
+    _fields_ = [('Nlevel', C.c_int32), ('reserved', C.c_int32), ('levels', C.POINTER(LsxLevel)), ('abundance', C.c_double)]
+
+
 # every symbol include/lsx.h declares
 REQUIRED_SYMBOLS = (
     'lsx_create', 'lsx_destroy', 'lsx_set_columns', 'lsx_formal_sol_gamma', 'lsx_stat_equil',
@@ -242,6 +246,10 @@ class LsxLibrary:
             d.lsx_hip_convert_scales.argtypes = [C.c_void_p, C.POINTER(LsxEosTables), C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp,
                                                  C.c_double, _dp, _dp, _dp, _dp, C.c_int32]
             d.lsx_hip_convert_scales.restype = C.c_int
+        self.has_eq_pops = hasattr(d, 'lsx_hip_eq_pops')               # include/lsx_hip_eqpops.h
+        if self.has_eq_pops:
+            d.lsx_hip_eq_pops.argtypes = [C.c_void_p, C.c_int32, C.POINTER(LsxEqAtom), C.c_int32, _dp, _dp, _dp, _dp, _dp]
+            d.lsx_hip_eq_pops.restype = C.c_int
         self.has_ng = hasattr(d, 'lsx_hip_ng_configure')               # include/lsx_hip_ng.h
         if self.has_ng:
             ip32 = C.POINTER(C.c_int32)

@@ -252,6 +252,7 @@ class Engine:
         self.serial = next(Engine._serials)      # this process's n-th engine: what per-engine bookkeeping keys on (never re-used, unlike id())
         self.problem = problem
         self.ncol = int(ncol)
+        self._have_atomic_data = False
         self._h = C.c_void_p()
         cprob, self._keep = problem.to_c()
         if isinstance(options, dict):
@@ -298,6 +299,15 @@ class Engine:
         cd, keep = data.to_c()
         self.lib.check(self.lib.dll.lsx_set_atomic_data(self._h, C.byref(cd)))
         del keep
+        self._have_atomic_data = True
+
+    def setup_columns(self, col0, model, setup, start_n=None):
+        """Columns [col0, col0 + model.ncol) from their atmosphere to a ready context, entirely through device entries
+        (native.setup_columns): placeholder set_columns, convert_scales(install), background(install), eq_pops for hydrogen and the
+        active atoms, set_atmosphere(lte_pops=True), and set(LSX_N, start_n) for a warm start.  model: native.ColumnModel; setup:
+        native.NativeSetup.  set_atomic_data is done on first use."""
+        from .native import setup_columns
+        return setup_columns(self, col0, model, setup, start_n=start_n)
 
     def set_atmosphere(self, col0, temperature, ne, vturb, nHGround, nTotal, vlos=None, lte_pops=False):
         """lsx_set_atmosphere for columns [col0, col0 + ncol): the library derives vBroad, aDamp, the line profiles, the
@@ -618,6 +628,32 @@ class Engine:
                                                            10**logG, opt(out[0]), opt(out[1]), opt(out[2]), opt(out[3]),
                                                            1 if install else 0))
         return Scales(*out) if want else None
+
+    def eq_pops(self, atoms, abundances, temperature, ne, nHTot, want_nTotal=True):
+        """LTE populations of any atoms, active in this engine or not: the reference's RadiativeSet.compute_eq_pops over
+        lte_pops(debye=True) (include/lsx_hip_eqpops.h, lsx_hip_eq_pops).  atoms: objects with .E_SI, .g and .stage per level
+        (atomdata.AtomData; only the levels are read); abundances: one per atom, relative to hydrogen; temperature, ne, nHTot
+        [ncol][Nspace] (SI; one column may be 1-D).
+        -> eqpops.EqPops with .nStar (a list per atom of [ncol][Nlevel][Nspace]), .nStar_flat [ncol][sum Nlevel][Nspace] and
+        .nTotal [ncol][natoms][Nspace] (None with want_nTotal=False).  For an atom that is active in the engine, nStar holds the
+        bits set_atmosphere(lte_pops=True) leaves in LSX_NSTAR.  Does not touch the engine's state; any ncol.  Only the HIP
+        library computes it."""
+        from .eqpops import EqPops, atoms_to_c
+        if not getattr(self.lib, 'has_eq_pops', False):
+            raise NotImplementedError('%s (%s) does not export lsx_hip_eq_pops: the LTE populations are computed by the HIP '
+                                      'library only' % (self.lib.path, self.lib.backend))
+        Ns = self.problem.Nspace
+        T = f64(np.asarray(temperature, dtype=np.float64).reshape(-1, Ns))
+        el, nH = f64(ne).reshape(-1, Ns), f64(nHTot).reshape(-1, Ns)
+        if el.shape != T.shape or nH.shape != T.shape:
+            raise ValueError('temperature, ne and nHTot differ in shape')
+        ncol = T.shape[0]
+        carr, nlev, _keep = atoms_to_c(atoms, abundances)
+        nStar = np.empty((ncol, int(sum(nlev)), Ns))
+        nTotal = np.empty((ncol, len(nlev), Ns)) if want_nTotal else None
+        self.lib.check(self.lib.dll.lsx_hip_eq_pops(self._h, len(nlev), carr, ncol, _ptr(T), _ptr(el), _ptr(nH), _ptr(nStar),
+                                                    None if nTotal is None else _ptr(nTotal)))
+        return EqPops(nStar, nTotal, nlev)
 
     def configure_ng(self, order=2, delay=0):
         """Ng acceleration of the populations behind every stat_equil of this engine (include/lsx_hip_ng.h, lsx_hip_ng_configure):

@@ -130,7 +130,6 @@ def run_response_function(prob: Problem, base: ColumnBlock, fixture: dict, ks, l
     ng (problem.NgOptions, default None: off): Ng acceleration of the populations in both solves (include/lsx_hip_ng.h); the
     options check of a sharded job then covers it."""
     from . import _capi, drivers
-    from .parallel import shard_columns
     from .problem import Engine
     e0 = Engine(prob, 1, device=device, lib=lib, stream=stream)
     if ng is not None and ng.order:
@@ -141,39 +140,119 @@ def run_response_function(prob: Problem, base: ColumnBlock, fixture: dict, ks, l
     it0 = [drivers.iterate_mali_engine(e0, log=log).n_iter]
     I_base, n_base = e0.get(_capi.LSX_I)[0], e0.get(_capi.LSX_N)[0]
     jobs = [(int(k), tag) for k in ks for tag in ('p', 'm')]
+
+    def fill(eng, first, count):
+        index = index_deltas(fixture)
+        batch = apply_deltas(prob, base, [(index.get((k, tag), {}), k) for k, tag in jobs[first:first + count]], start_n=n_base)
+        for a in range(0, batch.ncol, 64):
+            eng.set_columns(a, batch.slice(a, min(batch.ncol, a + 64)))
+    I, n_iter, _, shard = _solve_perturbed(prob, e0, len(jobs), fill, lib=lib, device=device, stream=stream, ng=ng, rank=rank, world=world,
+                                           all_done=all_done, gather=gather, log=log, who='run_response_function')
+    rf = drivers.response_function(I[0::2], I[1::2], I_base, mu_index=mu_index)
+    return dict(rf=rf, I_base=I_base, n_base=n_base, n_iter_base=int(it0[0]), n_iter=n_iter, I=I, shard=shard)
+
+
+def _solve_perturbed(prob, e0, njobs, fill, lib=None, device=0, stream=None, ng=None, rank=0, world=1, all_done=None, gather=None,
+                     log=None, extras=None, who='response function'):
+    """The second half of a response function, shared by run_response_function and native_response_function: shard the njobs
+    perturbed columns over the ranks, fill(engine, first, count) this rank's engine, iterate every column with its own stopping rule,
+    gather.  e0: the converged base engine (the start-up check of a sharded job is made on it; it is closed here).
+    extras: {name: f(engine) -> array with a leading column axis}, evaluated on the converged batch and gathered like I
+    (f(None) -> the array of no columns, for a rank with an empty shard).
+    -> (I [njobs][Nspect][Nrays], n_iter [njobs], {name: array}, (first, count))"""
+    from . import _capi, drivers
+    from .parallel import shard_columns
+    from .problem import Engine
     if world > 1:
         # start-up check of the sharded job: every rank's engines must be made alike (options, rule, plan, and the mapping the
         # whole problem's column count selects) -- on the base engine, which every rank has, even one with an empty shard
         from .parallel import check_same_options
-        e0.set_sweep_policy('auto', len(jobs))
+        e0.set_sweep_policy('auto', njobs)
         check_same_options(e0)
     e0.close()
-    first, count = shard_columns(len(jobs), rank, world)
-    mine = jobs[first:first + count]
-    if mine:
-        index = index_deltas(fixture)
-        batch = apply_deltas(prob, base, [(index.get((k, tag), {}), k) for k, tag in mine], start_n=n_base)
-        # the kernel choice belongs to the problem -- all 2 len(ks) perturbed columns -- not to this rank's shard of it
-        eng = Engine(prob, batch.ncol, device=device, lib=lib, stream=stream, policy_columns=len(jobs))
+    first, count = shard_columns(njobs, rank, world)
+    extra = {}
+    if count:
+        # the kernel choice belongs to the problem -- all njobs perturbed columns -- not to this rank's shard of it
+        eng = Engine(prob, count, device=device, lib=lib, stream=stream, policy_columns=njobs)
         if ng is not None and ng.order:
             eng.configure_ng(ng)
-        for a in range(0, batch.ncol, 64):
-            eng.set_columns(a, batch.slice(a, min(batch.ncol, a + 64)))
+        fill(eng, first, count)
         n_iter = drivers.iterate_mali_columns(eng, log=log, all_done=all_done)
         I = eng.get(_capi.LSX_I)
+        for name, f in (extras or {}).items():
+            extra[name] = f(eng)
         eng.close()
     else:                                   # more ranks than columns: keep the collectives matched
         n_iter = np.zeros(0, dtype=np.int64)
         I = np.zeros((0, prob.Nspect, prob.Nrays))
+        for name, f in (extras or {}).items():
+            extra[name] = f(None)
         if all_done is not None:
             while not all_done(True):
                 pass
     if world > 1:
         if gather is None:
-            raise ValueError('run_response_function over several ranks needs gather=')
+            raise ValueError('%s over several ranks needs gather=' % who)
+        for name in sorted(extra):
+            extra[name] = gather(extra[name], n_iter)[0]
         I, n_iter = gather(I, n_iter)
-    rf = drivers.response_function(I[0::2], I[1::2], I_base, mu_index=mu_index)
-    return dict(rf=rf, I_base=I_base, n_base=n_base, n_iter_base=int(it0[0]), n_iter=n_iter, I=I, shard=(first, count))
+    return I, n_iter, extra, (first, count)
+
+
+def native_response_function(prob: Problem, setup, model, parameter='temperature', amplitude=50.0, ks=None, mu_index=-1, mus=None,
+                             ng=None, lib=None, device=0, rank=0, world=1, all_done=None, gather=None, stream=None, log=None):
+    """The response function of ANY column to a perturbation of one of its parameters, with every input of every column made on the
+    device (native.setup_columns): no fixture, no input from the reference.
+    setup: native.NativeSetup.  model: native.ColumnModel of ONE column.  parameter: 'temperature', 'vturb', 'vlos', 'ne' or
+    'nHTot' ('vlos' needs a problem that is not phi_compact); amplitude: the full size of the perturbation in the parameter's SI
+    unit -- column 2i is the model with q[ks[i]] + amplitude / 2, column 2i + 1 the one with q[ks[i]] - amplitude / 2, the job order
+    of run_response_function.  ks: the depths perturbed (None: all).
+    The base column is set up natively and iterated to convergence; the 2 len(ks) perturbed columns are set up natively, warm
+    started from its populations, and iterated each with its own stopping rule (sharded over ranks as run_response_function does).
+    -> the keys of run_response_function -- rf [Nspect][len(ks)] = (I+ - I-) / I_base at mu_index, I_base, n_base, n_iter_base,
+    n_iter, I, shard -- plus n (the perturbed columns' converged populations) and mus.  With mus= (direction cosines in (0, 1],
+    any number) rf is taken at those viewing angles instead, through Engine.emergent_rays on the converged batch and base: rf
+    [Nspect][len(ks)][nmu], and I_mus [2 len(ks)][Nspect][nmu], I_base_mus [Nspect][nmu]."""
+    from . import _capi, drivers
+    from .native import PARAMETERS, perturbed
+    from .problem import Engine
+    if parameter not in PARAMETERS:
+        raise ValueError('native_response_function: parameter %r; there are %s' % (parameter, ', '.join(PARAMETERS)))
+    m = model.validated(prob.Nspace)
+    if m.ncol != 1:
+        raise ValueError('native_response_function: the model holds %d columns; it takes one' % m.ncol)
+    ks = list(range(prob.Nspace)) if ks is None else [int(k) for k in ks]
+    if any(k < 0 or k >= prob.Nspace for k in ks):
+        raise ValueError('native_response_function: ks outside [0, %d)' % prob.Nspace)
+    if parameter == 'vlos' and prob.phi_compact:
+        raise ValueError('native_response_function: a phi_compact problem has no line-of-sight velocity to perturb')
+    mu = None if mus is None else np.atleast_1d(np.asarray(mus, dtype=np.float64)).reshape(-1)
+    e0 = Engine(prob, 1, device=device, lib=lib, stream=stream)
+    if ng is not None and ng.order:
+        e0.configure_ng(ng)
+    e0.setup_columns(0, m, setup)
+    it0 = drivers.iterate_mali_engine(e0, log=log).n_iter
+    I_base, n_base = e0.get(_capi.LSX_I)[0], e0.get(_capi.LSX_N)[0]
+    I_base_mus = None if mu is None else e0.emergent_rays(mu)[0]
+    batch = perturbed(m, parameter, float(amplitude), ks)
+
+    def fill(eng, first, count):
+        eng.setup_columns(0, batch.slice(first, first + count), setup, start_n=n_base)
+    extras = {'n': lambda eng: np.zeros((0, prob.NLtot, prob.Nspace)) if eng is None else eng.get(_capi.LSX_N)}
+    if mu is not None:
+        extras['I_mus'] = lambda eng: np.zeros((0, prob.Nspect, mu.shape[0])) if eng is None else eng.emergent_rays(mu)
+    I, n_iter, extra, shard = _solve_perturbed(prob, e0, 2 * len(ks), fill, lib=lib, device=device, stream=stream, ng=ng, rank=rank,
+                                               world=world, all_done=all_done, gather=gather, log=log, extras=extras,
+                                               who='native_response_function')
+    out = dict(I_base=I_base, n_base=n_base, n_iter_base=int(it0), n_iter=n_iter, I=I, shard=shard, n=extra['n'], mus=mu)
+    if mu is None:
+        out['rf'] = drivers.response_function(I[0::2], I[1::2], I_base, mu_index=mu_index)
+    else:
+        Im = extra['I_mus']
+        out.update(I_mus=Im, I_base_mus=I_base_mus,
+                   rf=np.stack([drivers.response_function(Im[0::2], Im[1::2], I_base_mus, mu_index=q) for q in range(mu.shape[0])], axis=-1))
+    return out
 
 
 def gather_over_ranks(group=None):
