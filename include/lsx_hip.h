@@ -49,6 +49,9 @@ int lsx_hip_emergent_rays(lsx_ctx* ctx, int32_t nmu, const double* mu, int32_t c
 /* LTE populations of any atoms, active in the context or not -- the reference's RadiativeSet.compute_eq_pops, which supplies
  * lsx_set_atmosphere's nHGround and nTotal: lsx_hip_eqpops.h, included below. */
 
+/* Time-dependent populations -- an implicit step of the rate equation dn/dt = Gamma n in the place of the statistical
+ * equilibrium: lsx_hip_timedep.h, included below. */
+
 /* GPU_MAX_HW_QUEUES=n for this process unless the caller has set it: call before the first HIP call. */
 int lsx_hip_request_hw_queues(int32_t n);
 
@@ -66,5 +69,6 @@ int lsx_hip_poison_lds(int32_t device, int32_t rounds);
 #include "lsx_hip_background.h"
 #include "lsx_hip_scales.h"
 #include "lsx_hip_eqpops.h"
+#include "lsx_hip_timedep.h"
 
 #endif /* LSX_HIP_H */

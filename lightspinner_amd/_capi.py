@@ -257,6 +257,16 @@ class LsxLibrary:
             d.lsx_hip_ng_configure.restype = C.c_int
             d.lsx_hip_ng_state.argtypes = [C.c_void_p, C.c_int32, C.c_int32, ip32, ip32, ip32, _dp]
             d.lsx_hip_ng_state.restype = C.c_int
+        self.has_time_dep = hasattr(d, 'lsx_hip_time_dep_start')       # include/lsx_hip_timedep.h
+        if self.has_time_dep:
+            d.lsx_hip_time_dep_start.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _dp, _dp]
+            d.lsx_hip_time_dep_start.restype = C.c_int
+            d.lsx_hip_time_dep_update_async.argtypes = [C.c_void_p]
+            d.lsx_hip_time_dep_update_async.restype = C.c_int
+            d.lsx_hip_time_dep_update.argtypes = [C.c_void_p, _dp]
+            d.lsx_hip_time_dep_update.restype = C.c_int
+            d.lsx_hip_time_dep_state.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _dp, _dp]
+            d.lsx_hip_time_dep_state.restype = C.c_int
 
     @property
     def backend(self):

@@ -85,6 +85,7 @@ struct lsx_ctx : lsxd::LsxPlan {        // the plan (lsx_plan.h: dimensions, tab
     bool opt_se_lds = false, opt_trace_classes = false, opt_serial = false;   // LSX_SE_LDS / LSX_TRACE_CLASSES / LSX_SERIAL, read once in lsx_create
     long fused_launches = 0;
     uint8_t* d_colmask = nullptr; // per-column activity, nullptr = all active
+    std::vector<uint8_t> colmask_host;   // host copy of the same (empty: all active)
     double *d_bgxchi = nullptr, *d_bgxeta = nullptr, *d_Psi2 = nullptr; // fast-continuum side arrays
     int* d_fast_tiles = nullptr;
     int *d_fast_cols[LSX_FGC_LISTS] = {}, *d_fast_rest = nullptr;
@@ -136,6 +137,10 @@ struct lsx_ctx : lsxd::LsxPlan {        // the plan (lsx_plan.h: dimensions, tab
     int32_t* d_ng_state = nullptr;       // [3][ncol]: counter, steps taken, steps rejected
     double* d_ng_coef = nullptr;         // [col][Natoms][2]: the coefficients of the last step taken
     int* d_ng_off = nullptr;             // [Natoms + 1]: where each atom's levels x depths start in a column's populations
+    // time-dependent populations (lsx_timedep.hip, include/lsx_hip_timedep.h): allocated by the first lsx_hip_time_dep_start
+    double* d_td_n_prev = nullptr;       // [col][NLtot][k]: the populations at the start of the column's time step
+    double* d_td_dt = nullptr;           // [col]: the time step, 0 = no step started
+    std::vector<double> td_dt;           // host copy of d_td_dt
     // staging
     double* d_stage = nullptr;
     size_t stage_doubles = 0;
@@ -206,5 +211,6 @@ void mark_profiles_set(lsx_ctx* c, size_t col0, size_t ncol);
 int ng_enqueue(lsx_ctx* c);                              // the step behind a statistical equilibrium, on the context's stream
 int ng_reset(lsx_ctx* c, size_t col0, size_t ncol);      // these columns' populations have been replaced: their history is discarded
 void ng_free(lsx_ctx* c);
+void td_free(lsx_ctx* c);                                // the state of the time-dependent step (lsx_timedep.hip)
 
 } // namespace lsxd

@@ -1336,6 +1336,7 @@ void lsx_destroy(lsx_ctx* c)
     if (c->h_pinned) (void)hipHostFree(c->h_pinned);
     if (c->h_n) (void)hipHostFree(c->h_n);
     ng_free(c);
+    td_free(c);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -2096,6 +2097,7 @@ int lsx_set_active_columns(lsx_ctx* c, const uint8_t* active)
     if (!active) {
         if (c->d_colmask) HIPCHK(hipFree(c->d_colmask));
         c->d_colmask = nullptr;
+        c->colmask_host.clear();
         return LSX_OK;
     }
     if (!c->d_colmask) {
@@ -2103,6 +2105,7 @@ int lsx_set_active_columns(lsx_ctx* c, const uint8_t* active)
         if (rc) return rc;
     }
     HIPCHK(hipMemcpy(c->d_colmask, active, (size_t)c->ncol, hipMemcpyHostToDevice));
+    c->colmask_host.assign(active, active + c->ncol);
     return LSX_OK;
 }
 

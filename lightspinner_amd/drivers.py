@@ -2,6 +2,7 @@
 
 D1  test.py:20-29 / response_fn.py:11-21  -- MALI iteration to convergence
 D2  response_fn.py:23-67                  -- brute-force temperature response function
+D3  (no counterpart in the reference)     -- time steps of the rate equation, each iterated to consistency with the radiation
 """
 from dataclasses import dataclass, field
 from typing import Callable, List, Optional
@@ -252,3 +253,43 @@ def iterate_mali_columns(engine, dJ_tol=2e-3, dPops_tol=1e-3, n_lambda_only=3, m
     if report is not None:
         report['nonfinite'] = np.flatnonzero(bad)
     return n_iter
+
+
+def advance_time_columns(engine, dt, nsteps=1, dJ_tol=2e-3, dPops_tol=1e-3, max_iter=200, all_done=None, log=None):
+    """`nsteps` time steps of the rate equation dn/dt = Gamma n for many independent columns (include/lsx_hip_timedep.h).  Per
+    step, every column starts from its current populations (Engine.time_dep_start; dt: seconds, a scalar or one value per column);
+    then formal solution + time_dep_update alternate until each column meets ITS tolerances, a column being frozen
+    (lsx_set_active_columns) as soon as it does, as in iterate_mali_columns.  There are no Lambda-only iterations: the populations
+    move from the first iteration on.  all_done(bool) -> bool: the multi-rank hook (logical AND over ranks), asked once per inner
+    iteration.  -> the inner iterations each column took in each step ([nsteps][ncol] int array)."""
+    from . import _capi
+    ncol = engine.ncol
+    counts = np.zeros((int(nsteps), ncol), dtype=np.int64)
+    for step in range(int(nsteps)):
+        engine.set_active_columns(None)
+        engine.time_dep_start(dt)
+        active = np.ones(ncol, dtype=bool)
+        dP = np.ones(ncol)
+        i = 0
+        while True:
+            i += 1
+            engine.formal_sol_gamma()
+            dJ = engine.get(_capi.LSX_DJ_COL)
+            engine.time_dep_update()
+            dP = np.where(active, engine.get(_capi.LSX_DPOPS_COL), dP)
+            counts[step, active] = i
+            with np.errstate(invalid='ignore'):
+                still = (dJ > dJ_tol) | (dP > dPops_tol)      # NaN compares False, as in iterate_mali_columns
+            active &= still
+            if i >= max_iter:
+                active[:] = False
+            done = not active.any()
+            if all_done is not None:
+                done = all_done(done)
+            if log:
+                log('Step %d, iteration %.3d: %d of %d columns still iterating' % (step + 1, i, int(active.sum()), ncol))
+            if done:
+                break
+            engine.set_active_columns(active)
+        engine.set_active_columns(None)
+    return counts

@@ -682,6 +682,49 @@ class Engine:
                                                      rj.ctypes.data_as(ip32), _ptr(coef)))
         return NgState(st, ap, rj, coef)
 
+    # ---- time-dependent populations (include/lsx_hip_timedep.h) ----
+    def _time_dep_lib(self, entry):
+        if not getattr(self.lib, 'has_time_dep', False):
+            raise NotImplementedError('%s (%s) does not export %s: the time-dependent step is taken by the HIP library only'
+                                      % (self.lib.path, self.lib.backend, entry))
+
+    def time_dep_start(self, dt, n_prev=None, col0=0, ncol=None):
+        """Begin a time step of `dt` seconds (a scalar, or one value per column) for columns [col0, col0 + ncol)
+        (lsx_hip_time_dep_start).  n_prev [ncol][NLtot][Nspace]: the populations at the start of the step; None: the columns'
+        current populations, copied on the device.  The populations themselves are not touched; the range's Ng history is
+        discarded.  Only the HIP library has it; there is no host version."""
+        self._time_dep_lib('lsx_hip_time_dep_start')
+        ncol = self.ncol - int(col0) if ncol is None else int(ncol)
+        if np.ndim(dt) == 0:
+            dts = np.full(max(ncol, 0), float(dt), dtype=np.float64)
+        else:
+            dts = f64(dt, (max(ncol, 0),))
+        prev = None if n_prev is None else f64(n_prev, (max(ncol, 0),) + self._shape(_capi.LSX_N))
+        self.lib.check(self.lib.dll.lsx_hip_time_dep_start(self._h, int(col0), ncol, _ptr(dts) if dts.size else None,
+                                                           None if prev is None else _ptr(prev)))
+
+    def time_dep_update(self) -> float:
+        """one implicit update of every active column's populations from the last formal solution's Gamma, in the place of
+        stat_equil (lsx_hip_time_dep_update) -> max relative population change against the iterate the call started from"""
+        self._time_dep_lib('lsx_hip_time_dep_update')
+        v = C.c_double()
+        self.lib.check(self.lib.dll.lsx_hip_time_dep_update(self._h, C.byref(v)))
+        return v.value
+
+    def time_dep_update_async(self):
+        """the same, enqueued: stands where stat_equil_async stands (sync, sync_begin / sync_end, fetch_populations follow as usual)"""
+        self._time_dep_lib('lsx_hip_time_dep_update_async')
+        self.lib.check(self.lib.dll.lsx_hip_time_dep_update_async(self._h))
+
+    def time_dep_state(self, col0=0, ncol=None):
+        """-> (dt [ncol], n_prev [ncol][NLtot][Nspace]) of columns [col0, col0 + ncol); dt = 0: no step started"""
+        self._time_dep_lib('lsx_hip_time_dep_state')
+        ncol = self.ncol - int(col0) if ncol is None else int(ncol)
+        dt = np.zeros(max(ncol, 0), dtype=np.float64)
+        prev = np.zeros((max(ncol, 0),) + self._shape(_capi.LSX_N), dtype=np.float64)
+        self.lib.check(self.lib.dll.lsx_hip_time_dep_state(self._h, int(col0), ncol, _ptr(dt), _ptr(prev)))
+        return dt, prev
+
     def gamma_of_atom(self, G, a):
         """view [ncol][Nl][Nl][Nspace] of atom a inside an LSX_GAMMA array"""
         p = self.problem

@@ -276,6 +276,7 @@ class Context:
         # stat_equil enqueues the next formal solution ahead where the library says that pays (one launch chain on one stream)
         self._lookahead = self._engine.prefers_lookahead() if lookahead is None else bool(lookahead)
         self._spec = False               # a speculative formal solution is enqueued and has not been accepted or taken back
+        self._td_step = None             # (prevTimePops, dt) of the time step time_dep_update has started
         self._n_synced = [np.array(a.n, dtype=np.float64) for a in self.activeAtoms]
         if self._handed['J']:
             self._J_synced = self._host['J'].copy()
@@ -506,11 +507,34 @@ class Context:
     def stat_equil(self) -> float:
         """rh_method.py:710-745 -> max relative population change; populations are written back IN
         PLACE into the arrays that alias eqPops[...].pops (rh_method.py:412-416, response_fn.py:62)"""
+        return self._population_update(self._engine.stat_equil_async, self._engine.stat_equil)
+
+    def time_dep_update(self, dt, prevTimePops=None):
+        """One implicit update of the populations over a time step of `dt` seconds from the last formal solution's Gamma, in the
+        place of stat_equil (include/lsx_hip_timedep.h) -> (dPops, prevTimePops).  The first call of a step, with
+        prevTimePops=None, starts the step from the current populations and returns them (a list with one [Nlevel][Nspace] array
+        per active atom, copies); later calls of the step pass that object back and iterate on.  Any other object -- or another
+        dt -- starts a step from the populations it holds.  The populations are written back in place like stat_equil's."""
+        self._cancel_lookahead()
+        self._push_host_edits()
+        eng = self._engine
+        if prevTimePops is None:
+            prevTimePops = [np.array(a.n, dtype=np.float64) for a in self.activeAtoms]
+            eng.time_dep_start(float(dt))
+            self._td_step = (prevTimePops, float(dt))
+        elif self._td_step is None or prevTimePops is not self._td_step[0] or float(dt) != self._td_step[1]:
+            prev = np.concatenate([np.asarray(p, dtype=np.float64) for p in prevTimePops], axis=0)
+            eng.time_dep_start(float(dt), n_prev=prev[None])
+            self._td_step = (prevTimePops, float(dt))
+        return self._population_update(eng.time_dep_update_async, eng.time_dep_update), prevTimePops
+
+    def _population_update(self, enqueue, blocking) -> float:
+        """a call that rewrites the populations from the last formal solution's Gamma, and their way back into the callers' arrays"""
         self._cancel_lookahead()                  # (a second stat_equil in a row works on the same Gamma, as in the reference)
         self._push_host_edits()
         eng = self._engine
         if self._lookahead:
-            eng.stat_equil_async()
+            enqueue()
             eng.sync_begin(populations=True)      # monitors + n, read back behind the solve ...
             try:
                 eng.formal_sol_gamma_speculative()    # ... and the next iteration's formal solution behind the read-back
@@ -524,7 +548,7 @@ class Context:
                 raise
             n = eng.fetch_populations()[0]
         else:
-            dPops = eng.stat_equil()
+            dPops = blocking()
             n = eng.get(_capi.LSX_N)[0]
         off = 0
         for a, atom in enumerate(self.activeAtoms):
