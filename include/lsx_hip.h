@@ -52,6 +52,8 @@ int lsx_hip_emergent_rays(lsx_ctx* ctx, int32_t nmu, const double* mu, int32_t c
 /* Time-dependent populations -- an implicit step of the rate equation dn/dt = Gamma n in the place of the statistical
  * equilibrium: lsx_hip_timedep.h, included below. */
 
+/* Launch counters of the kernels behind the sweep (introspection for the tests): lsx_hip_epilogue.h, included below. */
+
 /* GPU_MAX_HW_QUEUES=n for this process unless the caller has set it: call before the first HIP call. */
 int lsx_hip_request_hw_queues(int32_t n);
 
@@ -70,5 +72,6 @@ int lsx_hip_poison_lds(int32_t device, int32_t rounds);
 #include "lsx_hip_scales.h"
 #include "lsx_hip_eqpops.h"
 #include "lsx_hip_timedep.h"
+#include "lsx_hip_epilogue.h"
 
 #endif /* LSX_HIP_H */

@@ -267,6 +267,10 @@ class LsxLibrary:
             d.lsx_hip_time_dep_update.restype = C.c_int
             d.lsx_hip_time_dep_state.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _dp, _dp]
             d.lsx_hip_time_dep_state.restype = C.c_int
+        self.has_epilogue_info = hasattr(d, 'lsx_hip_epilogue_info')   # include/lsx_hip_epilogue.h
+        if self.has_epilogue_info:
+            d.lsx_hip_epilogue_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+            d.lsx_hip_epilogue_info.restype = C.c_int32
 
     @property
     def backend(self):

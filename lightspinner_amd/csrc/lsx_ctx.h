@@ -34,6 +34,22 @@ struct SweepClass : lsxd::PlanClass {   // a plan class + what the runtime keeps
     hipEvent_t done = nullptr;
 };
 
+// launches of the kernels behind the sweep since the context was made (introspection for the tests: lsx_hip_epilogue_info,
+// tests/test_epilogue_instances.py); kept beside SweepClass::launches and counted where those are
+struct EpilogueLaunches {
+    long rows[LSX_FAST_ROWS_NINST] = {};   // k_fast_gamma<LP, NT, SEG>, by lsx_fast_rows_index
+    long cols[LSX_FGC_LISTS] = {};         // k_fast_gamma_cols / k_fast_gamma_cols_big, per tile list
+    long prepass[2] = {};                  // k_fast_prepass<SEG>
+    long finish[3] = {};                   // k_gamma_finish_small, k_gamma_finish_levels, k_gamma_finish
+    void add(const EpilogueLaunches& a, const EpilogueLaunches& b)      // += a - b
+    {
+        for (int i = 0; i < LSX_FAST_ROWS_NINST; ++i) rows[i] += a.rows[i] - b.rows[i];
+        for (int i = 0; i < LSX_FGC_LISTS; ++i) cols[i] += a.cols[i] - b.cols[i];
+        for (int i = 0; i < 2; ++i) prepass[i] += a.prepass[i] - b.prepass[i];
+        for (int i = 0; i < 3; ++i) finish[i] += a.finish[i] - b.finish[i];
+    }
+};
+
 struct FsGraphKey {            // what a captured formal solution's kernel arguments depend on beyond the context's fixed state
     int jcur; const void* results; int clear_dp, solver, policy, policy_columns; const void* colmask;
     bool operator==(const FsGraphKey& o) const
@@ -67,6 +83,7 @@ struct lsx_ctx : lsxd::LsxPlan {        // the plan (lsx_plan.h: dimensions, tab
     bool opt_finish_big = false;     // LSX_FINISH_BIG=1: the many-column Gamma epilogue also for small batches (tests)
     bool opt_graph = false;          // LSX_GRAPH=1: a formal solution's launches as a captured HIP graph (enqueue_fs; measurement)
     std::vector<std::pair<FsGraphKey, hipGraphExec_t>> fs_graphs;
+    std::vector<EpilogueLaunches> fs_graph_epi;   // ... and the epilogue launches each of them replays
     bool opt_fused_epilogue = false; // LSX_FUSED_EPILOGUE=1: the fused launch also runs its fast tiles' Gamma epilogue (measured: slower, see enqueue_fs)
     int opt_abl_fast = 0;            // LSX_ABL_FUSED_FAST: timing ablations of the fused launch's fast-continuum work
     bool opt_no_fused_fast = false;  // LSX_NO_FUSED_FAST=1: small batches launch the fast-continuum kernels around the fused sweep (tests)
@@ -84,6 +101,7 @@ struct lsx_ctx : lsxd::LsxPlan {        // the plan (lsx_plan.h: dimensions, tab
     int policy_columns = 0;              // ... and, under AUTO, the column count that decides (0: this context's own)
     bool opt_se_lds = false, opt_trace_classes = false, opt_serial = false;   // LSX_SE_LDS / LSX_TRACE_CLASSES / LSX_SERIAL, read once in lsx_create
     long fused_launches = 0;
+    EpilogueLaunches epi_launches;
     uint8_t* d_colmask = nullptr; // per-column activity, nullptr = all active
     std::vector<uint8_t> colmask_host;   // host copy of the same (empty: all active)
     double *d_bgxchi = nullptr, *d_bgxeta = nullptr, *d_Psi2 = nullptr; // fast-continuum side arrays

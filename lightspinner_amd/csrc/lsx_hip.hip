@@ -1800,8 +1800,11 @@ static int enqueue_fs(lsx_ctx* c, bool timed, bool speculative = false)
         fq.fast_tiles = d_list; fq.n_fast_tiles = (int)n;
         fq.seg_depths = S.prepass_seg;
         dim3 grid((unsigned)n, (unsigned)c->ncol);
-        if (S.prepass_seg < c->Nspace) hipLaunchKernelGGL((k_fast_prepass<true>), grid, dim3(256), S.prepass_lds, st, fq);
-        else hipLaunchKernelGGL((k_fast_prepass<false>), grid, dim3(256), S.prepass_lds, st, fq);
+        c->epi_launches.prepass[S.prepass_seg < c->Nspace ? 1 : 0]++;
+        const bool seg = S.prepass_seg < c->Nspace;
+#define LSX_FP(SEGV) if (seg == SEGV) hipLaunchKernelGGL((k_fast_prepass<SEGV>), grid, dim3(256), S.prepass_lds, st, fq);
+        LSX_FAST_PREPASS_INSTANCES(LSX_FP)      // lsx_plan.h
+#undef LSX_FP
     };
     auto launch_fast_rows = [&](hipStream_t st, const int* d_list, size_t n) {
         FastParams fq = ff;
@@ -1813,27 +1816,28 @@ static int enqueue_fs(lsx_ctx* c, bool timed, bool speculative = false)
         const bool seg = fq.seg_depths < c->Nspace;
 #define LSX_FG(LPV, NTV) if (LP == LPV && nt == NTV) { if (seg) hipLaunchKernelGGL((k_fast_gamma<LPV, NTV, true>), grid, dim3(NTV), sm, st, fq); \
                                                        else hipLaunchKernelGGL((k_fast_gamma<LPV, NTV, false>), grid, dim3(NTV), sm, st, fq); }
-        LSX_FG(16, 256); LSX_FG(16, 128); LSX_FG(16, 64);
-        LSX_FG(32, 256); LSX_FG(32, 128); LSX_FG(32, 64);
-        LSX_FG(64, 256); LSX_FG(64, 128); LSX_FG(64, 64);
+        LSX_FAST_ROWS_INSTANCES(LSX_FG)         // lsx_plan.h
 #undef LSX_FG
+        const int ri = lsx_fast_rows_index(LP, nt, seg);
+        if (ri >= 0) c->epi_launches.rows[ri]++;
     };
     // the column-mapped kernel: two lanes per (column, depth), blocks of 256 over the columns' depths x the tiles
     auto launch_fast_cols = [&](hipStream_t st, const int* d_list, size_t n, int v, bool epi) {
         FastParams fq = ff;
         fq.epi_corr = epi ? 1 : 0;
         fq.fast_tiles = d_list; fq.n_fast_tiles = (int)n;
+        c->epi_launches.cols[v]++;
         if (v >= 4) {       // big sets: two waves per workgroup
             dim3 gridb((unsigned)(((size_t)c->ncol * c->Nspace + 2 * LSX_FGC_ROWS - 1) / (2 * LSX_FGC_ROWS)), (unsigned)n);
 #define LSX_FC(NLCV) if (fgc_lines(v) == NLCV) hipLaunchKernelGGL((k_fast_gamma_cols_big<NLCV>), gridb, dim3(128), S.cols_lds[v], st, fq);
-            LSX_FC(0) LSX_FC(1) LSX_FC(2)
+            LSX_FAST_COLS_BIG_INSTANCES(LSX_FC)
 #undef LSX_FC
             return;
         }
         dim3 grid((unsigned)(((size_t)c->ncol * c->Nspace + 4 * LSX_FGC_ROWS - 1) / (4 * LSX_FGC_ROWS)), (unsigned)n);
-#define LSX_FC(NLCV) if (kLkLines[v] == NLCV) { if (c->L == 12) hipLaunchKernelGGL((k_fast_gamma_cols<NLCV, 6>), grid, dim3(256), S.cols_lds[v], st, fq); \
-                                                else hipLaunchKernelGGL((k_fast_gamma_cols<NLCV, 0>), grid, dim3(256), S.cols_lds[v], st, fq); }
-        LSX_FC(0) LSX_FC(1) LSX_FC(2)
+        const int npc = c->L == 12 ? 6 : 0;
+#define LSX_FC(NLCV, NPCV) if (kLkLines[v] == NLCV && npc == NPCV) hipLaunchKernelGGL((k_fast_gamma_cols<NLCV, NPCV>), grid, dim3(256), S.cols_lds[v], st, fq);
+        LSX_FAST_COLS_INSTANCES(LSX_FC)
 #undef LSX_FC
     };
     auto launch_fast_gamma = [&](hipStream_t st, const std::vector<int>* cols, int* const* d_cols, const int* d_rest, size_t nrest, bool epi = false) {
@@ -1869,9 +1873,12 @@ static int enqueue_fs(lsx_ctx* c, bool timed, bool speculative = false)
             capturing = lerr == hipSuccess;
         }
     }
+    const EpilogueLaunches epi_before = c->epi_launches;
     if (gexec) {
         if (!per_class_launches(c)) c->fused_launches++;
         else for (auto& k : c->classes) k.launches++;
+        for (size_t g = 0; g < c->fs_graphs.size(); ++g)
+            if (c->fs_graphs[g].first == gkey) c->epi_launches.add(c->fs_graph_epi[g], EpilogueLaunches());
     } else {
     if (!per_class_launches(c)) {
         p.ncell_lev = S.fused_ncell_lev; p.ncell_atom = S.fused_ncell_atom;
@@ -1953,6 +1960,7 @@ static int enqueue_fs(lsx_ctx* c, bool timed, bool speculative = false)
     // the next stat_equil clears them itself.  (A speculative call writes the second block: nothing pending there.)
     f.clear_dp = clear_dp;
     const long nthreads = (long)c->ncol * c->Nspace;
+    c->epi_launches.finish[(c->ncol < 32 && !c->opt_finish_big) ? 0 : (S.finish_w > 0 ? 1 : 2)]++;
     if (c->ncol < 32 && !c->opt_finish_big)
         hipLaunchKernelGGL(k_gamma_finish_small, dim3((unsigned)nthreads), dim3(64), (size_t)c->NL2tot * sizeof(double), c->stream, f);
     else if (S.finish_w > 0) {
@@ -1966,7 +1974,11 @@ static int enqueue_fs(lsx_ctx* c, bool timed, bool speculative = false)
         note(hipStreamEndCapture(c->stream, &g));
         if (lerr == hipSuccess) note(hipGraphInstantiate(&gexec, g, nullptr, nullptr, 0));
         if (g) (void)hipGraphDestroy(g);
-        if (lerr == hipSuccess) c->fs_graphs.emplace_back(gkey, gexec);
+        if (lerr == hipSuccess) {
+            c->fs_graphs.emplace_back(gkey, gexec);
+            c->fs_graph_epi.emplace_back();
+            c->fs_graph_epi.back().add(c->epi_launches, epi_before);
+        }
     }
     if (gexec) note(hipGraphLaunch(gexec, c->stream));
     c->dp_zeroed = clear_dp != 0;
@@ -2650,6 +2662,22 @@ int32_t lsx_hip_class_info(const lsx_ctx* c, int32_t idx, int64_t* out)
         out[6] = ((c->solver == LSX_SOLVER_PARABOLIC ? k.rsp : k.rs) && use_ray_serial(c)) ? 1 : 0;
     }
     return (int32_t)c->classes.size();
+}
+
+// HIP-only introspection for the tests (include/lsx_hip.h): launches of the kernels behind the sweep since the context was made.
+int32_t lsx_hip_epilogue_info(const lsx_ctx* c, int64_t* out)
+{
+    if (!c || !out) return 0;
+    const EpilogueLaunches& e = c->epi_launches;
+    int n = 0, i = 0;
+#define LSX_X(LPV, NTV) out[n++] = lsx_fast_rows_code(LPV, NTV, false); out[n++] = e.rows[2 * i]; out[n++] = lsx_fast_rows_code(LPV, NTV, true); out[n++] = e.rows[2 * i + 1]; ++i;
+    LSX_FAST_ROWS_INSTANCES(LSX_X)
+#undef LSX_X
+    for (int v = 0; v < LSX_FGC_LISTS; ++v) out[n++] = e.cols[v];
+    out[n++] = e.prepass[0]; out[n++] = e.prepass[1];
+    out[n++] = e.finish[0]; out[n++] = e.finish[1]; out[n++] = e.finish[2];
+    out[n++] = c->shapes.finish_nt;
+    return n;
 }
 
 // diagnostic (tests/test_lds_hygiene.py): fill the LDS of every CU with signalling garbage.  LDS keeps its contents from one kernel

@@ -52,6 +52,35 @@ inline bool lsx_sweep_instance_exists(int npt, int nl, bool lk, int topo)
     }
 }
 
+// ---- the compiled instances of the fast-continuum epilogue (lsx_hip.hip), ONE list each: enqueue_fs expands them into the launch
+// switches, lsx_plan_epilogue_instances (lsx_plan_capi.cpp) hands them to tests/test_epilogue_ledger.py -- every instance must be
+// planned, and run against the oracle, by a case of tests/epilogue_cases.py or be shown unreachable there.
+//   k_fast_gamma<LP, NT, SEG> (row mapped): X(LP, NT), each for SEG = false and true (LaunchShapes::rows_lp / rows_nt / rows_seg)
+#define LSX_FAST_ROWS_INSTANCES(X)                                                                               \
+    X(16, 256) X(16, 128) X(16, 64)                                                                              \
+    X(32, 256) X(32, 128) X(32, 64)                                                                              \
+    X(64, 256) X(64, 128) X(64, 64)
+//   k_fast_gamma_cols<NLC, NPC> (column mapped): lines fed by linked continua, NPC = 6 for tiles of twelve wavelengths, else 0
+#define LSX_FAST_COLS_INSTANCES(X) X(0, 6) X(0, 0) X(1, 6) X(1, 0) X(2, 6) X(2, 0)
+//   k_fast_gamma_cols_big<NLC> (column mapped, big sets)
+#define LSX_FAST_COLS_BIG_INSTANCES(X) X(0) X(1) X(2)
+//   k_fast_prepass<SEG> (SEG first: the order in which the launch switch has always instantiated them, i.e. their order in the code object)
+#define LSX_FAST_PREPASS_INSTANCES(X) X(true) X(false)
+constexpr int lsx_fast_rows_code(int lp, int nt, bool seg) { return lp * 1024 + nt * 2 + (seg ? 1 : 0); }
+constexpr int lsx_fast_cols_code(int nlc, int npc) { return nlc * 16 + npc; }
+#define LSX_X(LPV, NTV) +2
+constexpr int LSX_FAST_ROWS_NINST = 0 LSX_FAST_ROWS_INSTANCES(LSX_X);      // every pair, SEG = false and true
+#undef LSX_X
+// position of a row-mapped instance in its list, SEG = false before SEG = true; -1: no such instance
+inline int lsx_fast_rows_index(int lp, int nt, bool seg)
+{
+    int i = 0;
+#define LSX_X(LPV, NTV) if (lp == LPV && nt == NTV) return 2 * i + (seg ? 1 : 0); ++i;
+    LSX_FAST_ROWS_INSTANCES(LSX_X)
+#undef LSX_X
+    return -1;
+}
+
 // ---- LDS layout of one sweep workgroup (doubles from the start of dynamic LDS), shared by the kernel (offsets) and the plan
 // (bytes to request).  The lane sums of the Gamma integrands are DPP / permlane trees (lsx_sweep.hip); their totals are parked in
 // the `tb` area, [2 waves][2 npt][64], until 64 depths can leave in one store.  Measured and not kept: the sums through a

@@ -216,6 +216,62 @@ int32_t lsx_plan_instances(int32_t which, int32_t* codes, int32_t max)
     return (int32_t)v.size();
 }
 
+// The compiled instances of the kernels behind the sweep, from the lists enqueue_fs expands (lsx_plan.h): which = 0 k_fast_gamma
+// (codes: lsx_fast_rows_code(LP, NT, SEG), SEG = false and true of every pair), 1 k_fast_gamma_cols (lsx_fast_cols_code(NLC, NPC)),
+// 2 k_fast_gamma_cols_big (NLC), 3 k_fast_prepass (SEG).  -> count.  tests/test_epilogue_ledger.py.
+int32_t lsx_plan_epilogue_instances(int32_t which, int32_t* codes, int32_t max)
+{
+    std::vector<int32_t> v;
+#define LSX_XR(LP, NT) v.push_back(lsx_fast_rows_code(LP, NT, false)); v.push_back(lsx_fast_rows_code(LP, NT, true));
+#define LSX_XC(NLC, NPC) v.push_back(lsx_fast_cols_code(NLC, NPC));
+#define LSX_X1(A) v.push_back((int32_t)(A));
+    if (which == 0) { LSX_FAST_ROWS_INSTANCES(LSX_XR) }
+    else if (which == 1) { LSX_FAST_COLS_INSTANCES(LSX_XC) }
+    else if (which == 2) { LSX_FAST_COLS_BIG_INSTANCES(LSX_X1) }
+    else if (which == 3) { LSX_FAST_PREPASS_INSTANCES(LSX_X1) }
+#undef LSX_XR
+#undef LSX_XC
+#undef LSX_X1
+    for (int32_t i = 0; codes && i < (int32_t)v.size() && i < max; ++i) codes[i] = v[i];
+    return (int32_t)v.size();
+}
+
+// Which of those instances a problem takes, read from the plan's own LaunchShapes and tile lists (nothing restated).  out[26]:
+//   [0] rows_lp  [1] rows_nt  [2] 1 if rows_seg < Nspace  [3] tiles of fast_rest  [4] ... of them not "simple" (the cell path)
+//   [5] 1 if the cells are part of the LDS layout (fast_generic)  [6] rows_seg  [7] rows_lds
+//   [8 .. 14] tiles of each column-mapped list  [15] 1 if prepass_seg < Nspace  [16] prepass_seg  [17] fast tiles
+//   [18] finish_w  [19] finish_nt  [20] L  [21] most lines fed by linked continua among the tiles of fast_rest  [22] nF_max
+//   [23] fewest wavelengths of a tile of fast_rest  [24] tile classes with tiles in fast_rest  [25] ... with fast continua at all
+//        (per-class launches: each of them launches the row-mapped kernel / the pre-pass once per formal solution)
+// -> LSX_OK or plan_build's error code (message in err).
+int lsx_plan_epilogue_shapes(const lsx_problem* d, uint32_t option_bits, int64_t* out, char* err, int32_t errlen)
+{
+    PlanOptions opt;
+    opt.no_linked = option_bits & 1; opt.natural_tiles = option_bits & 2; opt.no_topo = option_bits & 4; opt.fast_rows = option_bits & 8;
+    opt.order_by_cost = option_bits & 16; opt.finish_lds = option_bits & 32;
+    LsxPlan P;
+    std::string e;
+    const int rc = plan_build(d, opt, &P, &e);
+    if (err && errlen > 0) { strncpy(err, e.c_str(), (size_t)errlen - 1); err[errlen - 1] = 0; }
+    if (rc) return rc;
+    const LaunchShapes& S = P.shapes;
+    int64_t cells = 0, lk = 0, nla_min = P.L + 1;
+    for (int t : P.fast_rest) {
+        cells += P.tiles[t].fast_simple == 0;
+        if (P.tiles[t].nK > 0) lk = std::max<int64_t>(lk, std::min<int>(P.tiles[t].nL, LSX_MAX_TILE_LINES));
+        nla_min = std::min<int64_t>(nla_min, P.tiles[t].nla);
+    }
+    const bool fast = !P.fast_tiles.empty();
+    out[24] = out[25] = 0;
+    for (auto& k : P.plan_classes) { out[24] += !k.fast_rest.empty(); out[25] += !k.fast_tiles.empty(); }
+    out[0] = S.rows_lp; out[1] = S.rows_nt; out[2] = fast && S.rows_seg < P.Nspace; out[3] = (int64_t)P.fast_rest.size(); out[4] = cells;
+    out[5] = P.fast_generic; out[6] = S.rows_seg; out[7] = (int64_t)S.rows_lds;
+    for (int v = 0; v < LSX_FGC_LISTS; ++v) out[8 + v] = (int64_t)P.fast_cols[v].size();
+    out[15] = fast && S.prepass_seg < P.Nspace; out[16] = S.prepass_seg; out[17] = (int64_t)P.fast_tiles.size();
+    out[18] = S.finish_w; out[19] = S.finish_nt; out[20] = P.L; out[21] = lk; out[22] = P.nF_max; out[23] = P.fast_rest.empty() ? 0 : nla_min;
+    return LSX_OK;
+}
+
 // the ray-serial eligibility of a problem's classes: -> number of classes; out[c][2] = class code, 1 if the class has a
 // ray-serial instance AND the context's shape admits the kernel (five rays, wavelength-independent scattering, 32-bit offsets),
 // + 2 if it has one for the parabolic rule as well

@@ -456,6 +456,19 @@ class Engine:
         self.lib.check(self.lib.dll.lsx_get(self._h, what, int(col0), int(ncol), _ptr(out), out.nbytes))
         return out
 
+    def epilogue_info(self):
+        """Launch counters of the kernels behind the sweep since the engine was made (include/lsx_hip_epilogue.h; HIP library only):
+        -> dict(rows={(lanes per depth row, threads, segmented): launches of the row-mapped fast-continuum epilogue, launched ones only},
+        cols=[launches per column-mapped tile list], prepass=(whole column, segmented), finish=dict(small=, levels=, lds=), finish_nt=)."""
+        if not getattr(self.lib, 'has_epilogue_info', False):
+            raise NotImplementedError('%s (%s) does not export lsx_hip_epilogue_info' % (self.lib.path, self.lib.backend))
+        out = (C.c_int64 * 64)()
+        n = self.lib.dll.lsx_hip_epilogue_info(self._h, out)
+        assert n == 49, n
+        v = [int(x) for x in out[:n]]
+        rows = {(v[i] >> 10, (v[i] & 1023) >> 1, bool(v[i] & 1)): v[i + 1] for i in range(0, 36, 2) if v[i + 1]}
+        return dict(rows=rows, cols=v[36:43], prepass=(v[43], v[44]), finish=dict(small=v[45], levels=v[46], lds=v[47]), finish_nt=v[48])
+
     def emergent_rays(self, mus, col0=0, ncol=None):
         """Emergent intensity at arbitrary viewing angles from what the engine holds (include/lsx_hip.h, lsx_hip_emergent_rays):
         one final-pass formal solution of the up-going rays with direction cosines `mus` (each in (0, 1], any number of them)
