@@ -13,6 +13,7 @@ under /root/reference is touched:
 (np.bool, used at rh_method.py:124, exists again in numpy 2.x.)
 
 Usage:  python tests/golden/make_golden.py [units] [falc_ca] [falc_cah] [falc_ca_vlos] [falc_c] [falc_fe] [falc_mg] [falc_all] [rf] [rf_inputs] [rf_outputs] [setup] [live_ref] [setup_atoms] [all]
+        python tests/golden/make_topology_golden.py [toy] [rs] [inst] [shallow] [bare] [dead] [all]      (topologies_*.npz: the made-up topologies)
 """
 import os
 import sys

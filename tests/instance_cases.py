@@ -1,7 +1,8 @@
 """The ledger of compiled sweep instances: every template instance of the sweep kernels that the
 product library compiles and can dispatch to -- lsx_sweep_kernel<NPT, NL, 5, SCAL, LK, TOPO> (one ray per lane),
 lsx_sweep_rs_kernel<NPT, NL, LK, TOPO> (ray-serial) and the parabolic rule's sweep_tile_par<...> -- must be reached by a GPU
-parity test against the oracle.  This module is the shared data of the two sides:
+parity test against the oracle -- and, for the linear rule, against the reference's own loop on the same columns
+(tests/test_topologies_reference.py, through the fixture tests/golden/topologies_*.npz).  This module is the shared data of the two sides:
 
   tests/test_instance_ledger.py (CPU)   walks the instance lists of lsx_plan.h (lsx_plan_instances) and the plans of the
                                         problems below (lsx_plan_probe) and fails if an instance is planned by none of them;
@@ -9,7 +10,7 @@ parity test against the oracle.  This module is the shared data of the two sides
                                         parabolic rule against the oracle and asserts that the expected instances did run.
 
 The topologies follow the reference's own multi-stage model atoms (rh_atoms.py:194 C_atom, :355 Fe_simple_atom: lines of the
-upper ionisation stage start on the level a lower stage's continua end on, rh_method.py:606-627, 654-681); nothing else here
+upper ionisation stage start on the level a lower stage's continua end on, rh_method.py:606-627, 654-681); no number here
 comes from the reference.  An atom: (Nlevel, [(kind, lower, upper, blue end, red end of its range as fractions of the spectrum)])."""
 from toy import spec_problem
 
@@ -55,13 +56,10 @@ CROWD = [(7, [('l', 0, u, 0.20 + 0.02 * u, 0.60 + 0.02 * u) for u in range(1, 6)
 TOPOLOGIES = dict(stages1=STAGES_1, stages2=STAGES_2, stages3=STAGES_3, multi_up=MULTI_UP, two_atoms=TWO_ATOMS, linked_up=LINKED_UP,
                   linked_low=LINKED_LOW, mixed=MIXED, triplet=TRIPLET, crowd=CROWD)
 
-# (topology, ncol, Nspace, phi_compact): >= 32 columns so that the per-class launches run (one kernel instance per tile class);
-# ragged column groups for the five-column wavefronts of the ray-serial kernel; odd and even depth counts
-CASES = [
-    ('stages1', 33, 31, False), ('stages2', 34, 40, False), ('stages3', 36, 33, False), ('multi_up', 37, 38, False),
-    ('two_atoms', 33, 35, False), ('linked_up', 34, 36, False), ('linked_low', 35, 29, True), ('mixed', 33, 34, False),
-    ('triplet', 32, 30, False), ('crowd', 33, 27, False),
-]
+# (topology, ncol, Nspace, phi_compact): the list lives in tests/topology_cases.py, the one table of made-up cases (>= 32 columns so that the
+# per-class launches run; ragged column groups for the five-column wavefronts of the ray-serial kernel; odd and even depth counts)
+from topology_cases import INSTANCE_CASES as CASES  # noqa: E402
+
 NSPECT = 260
 
 

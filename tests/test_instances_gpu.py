@@ -17,6 +17,7 @@ import pytest
 import envelope
 from conftest import relerr, gamma_err
 import instance_cases as ic
+import topology_cases as tc
 from lightspinner_amd import _capi
 from lightspinner_amd.problem import Engine
 
@@ -83,12 +84,13 @@ def test_case_meets_the_oracle(hip_lib, oracle_lib, case, mode):
 
 
 @pytest.mark.parametrize('mode', ['lane', 'serial', 'parabolic', 'parabolic-serial'])
-@pytest.mark.parametrize('Ns', [3, 4, 5, 6])
+@pytest.mark.parametrize('Ns', tc.SHALLOW_DEPTHS)
 def test_shallow_columns_meet_the_oracle(hip_lib, oracle_lib, Ns, mode):
     """the smallest atmospheres lsx_create admits (Nspace >= 3, formal_solver.py:120-139): the first point, the meeting point of the two
     directions and the end point fall into neighbouring steps -- three depths: the midpoint's step is the last one; four: no midpoint --
     on every mapping and both rules (the parabolic rule runs one depth behind the opacities: its last request must not leave the column)"""
-    prob, block = ic.build('two_atoms', 33, Ns, False)
+    prob, block = tc.build('shallow-%d' % Ns)
+    assert block.ncol == 33
     eh = Engine(prob, 33, lib=hip_lib, sweep_policy='ray-serial' if mode.endswith('serial') else 'ray-per-lane')
     eo = Engine(prob, 33, lib=oracle_lib)
     for e in (eh, eo):
@@ -120,13 +122,11 @@ def test_shallow_columns_meet_the_oracle(hip_lib, oracle_lib, Ns, mode):
     eh.close(); eo.close()
 
 
-@pytest.mark.parametrize('ncol', [3, 40])
+@pytest.mark.parametrize('ncol', tc.BARE_NCOL)
 def test_atom_without_radiative_transitions(hip_lib, oracle_lib, ncol):
     """three atoms, the middle one with collisions only: its Gamma is its C with the diagonal of rh_method.py:698-703 -- the Gamma epilogue
     runs per (column, depth, atom) and that atom's slot list is empty (fewer than 32 columns: the small-batch epilogue)"""
-    from toy import spec_problem
-    atoms = [(3, [('l', 0, 1, 0.1, 0.5), ('c', 1, 2, 0.0, 0.3)]), (2, []), (3, [('l', 0, 2, 0.4, 0.9), ('c', 0, 2, 0.0, 0.2)])]
-    prob, block = spec_problem(atoms, seed=5, Nspace=30, Nrays=5, Nspect=200, ncol=ncol)
+    prob, block = tc.build('bare-%d' % ncol)
     eh, eo = Engine(prob, ncol, lib=hip_lib), Engine(prob, ncol, lib=oracle_lib)
     for e in (eh, eo):
         e.set_columns(0, block)

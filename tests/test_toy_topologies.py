@@ -9,31 +9,9 @@ import pytest
 import envelope
 from conftest import relerr, gamma_err
 from toy import toy_problem
+from topology_cases import CASES, RS_CASES        # (the table the reference's own loop is driven on: tests/topology_cases.py)
 from lightspinner_amd import _capi
 from lightspinner_amd.problem import Engine
-
-CASES = [
-    dict(seed=1),                                                     # 3 rays, 37 depths, chained continua
-    dict(seed=2, Nrays=1, Nspace=20, Nspect=70),                      # 64 wavelengths per wavefront
-    dict(seed=3, Nrays=5, Nspace=82, Nspect=130, sca_per_lambda=True),
-    dict(seed=4, phi_compact=True, chain=False),
-    dict(seed=5, Nrays=2, Nspace=5, Nspect=40, ncol=40),              # shortest useful column; >= 32 columns: per-class launches
-    dict(seed=6, Nrays=7, Nspace=33, Nspect=55, ncol=33),
-    dict(seed=7, Nrays=8, Nspace=21, Nspect=48, ncol=2),              # 8 wavelengths per wavefront, all 64 lanes used
-    dict(seed=8, Nrays=3, Nspace=700, Nspect=30, ncol=33),            # deep column: the operand table no longer fits LDS -> generic instance
-    dict(seed=9, Nrays=3, Nspace=700, Nspect=30, ncol=2),             # same through the fused small-batch launch
-    # regular bound-free sets on even tile widths: the column-mapped epilogue (k_fast_gamma_cols), with linked continua
-    dict(seed=10, Nrays=4, Nspace=45, Nspect=100, ncol=34, chain=False),
-    dict(seed=11, Nrays=5, Nspace=82, Nspect=140, ncol=3, chain=False),
-    dict(seed=12, Nrays=8, Nspace=31, Nspect=64, ncol=33, chain=False, phi_compact=True),
-    # multiplets under linked continua: three per-ray slots (the <3, 3, linked> instance) and four (no such instance: the plan
-    # files the tile under the generic linked kernel), through the per-class launches (>= 32 columns) and the fused launch
-    dict(seed=13, Nrays=5, Nspace=41, Nspect=120, ncol=34, multiplet=3),
-    dict(seed=14, Nrays=5, Nspace=41, Nspect=120, ncol=3, multiplet=3),
-    dict(seed=15, Nrays=5, Nspace=41, Nspect=120, ncol=34, multiplet=4),
-    dict(seed=16, Nrays=5, Nspace=41, Nspect=120, ncol=3, multiplet=4),
-    dict(seed=17, Nrays=3, Nspace=30, Nspect=150, ncol=33, multiplet=4, phi_compact=True),
-]
 
 
 def _run(lib, prob, block, iters, solver='linear'):
@@ -115,15 +93,6 @@ def _classes_on_ray_serial(lib, eng):
         if out[6] and out[3] > 0:
             rs.append((int(out[0]), int(out[1]), int(out[4]), int(out[5])))
     return rs
-
-
-RS_CASES = [
-    dict(seed=11, Nrays=5, Nspace=82, Nspect=140, ncol=33, chain=False),        # 33 columns: six full groups of five and one of three
-    dict(seed=13, Nrays=5, Nspace=41, Nspect=120, ncol=34, multiplet=3),        # odd depth count: the two directions meet in one step
-    dict(seed=15, Nrays=5, Nspace=41, Nspect=120, ncol=37, multiplet=4),        # four-line multiplets (generic class beside the ray-serial ones)
-    dict(seed=21, Nrays=5, Nspace=3, Nspect=60, ncol=36),                       # the shortest column the rule allows
-    dict(seed=22, Nrays=5, Nspace=30, Nspect=90, ncol=41, phi_compact=True),    # ray-independent profiles
-]
 
 
 @pytest.mark.gpu

@@ -1,5 +1,7 @@
-"""Small made-up model atoms with awkward level topologies, for HIP-vs-oracle parity on shapes the FALC
-fixtures do not reach (the oracle itself is pinned on the reference's own atoms, tests/test_oracle_golden.py):
+"""Small made-up model atoms with awkward level topologies, for parity on shapes the FALC fixtures do not reach.  HIP and
+the oracle are compared on them (tests/test_toy_topologies.py, tests/test_instances_gpu.py), and both with the reference's own
+loop driven on the same arrays (tests/topology_cases.py names the cases, tests/golden/make_topology_golden.py runs the
+reference on them, tests/test_topologies_reference_host.py and tests/test_topologies_reference.py compare):
 
   * lines sharing a lower level and overlapping in wavelength,
   * a continuum whose lower level is another continuum's upper level (chained ionisation stages), so the
@@ -7,7 +9,7 @@ fixtures do not reach (the oracle itself is pinned on the reference's own atoms,
   * an atom with continua only,
   * odd Nspace, 1 / 3 / 5 rays (64 / 21 / 12 wavelengths per wavefront), per-wavelength scattering.
 
-Nothing here comes from the reference; the numbers only need to give a well-posed transfer problem.
+No number here comes from the reference; they only need to give a well-posed transfer problem.
 """
 import numpy as np
 
