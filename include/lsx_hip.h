@@ -33,6 +33,9 @@ int lsx_hip_emergent_rays(lsx_ctx* ctx, int32_t nmu, const double* mu, int32_t c
 
 /* Radiative rates Rij / Rji of every transition from what a context holds: lsx_hip_rates.h, included below. */
 
+/* Radiative flux, net radiative cooling and its division among the transitions from what a context holds: lsx_hip_losses.h,
+ * included below. */
+
 /* Opacity, source function, optical depth, intensity and contribution function at every depth along arbitrary rays:
  * lsx_hip_depth.h, included below. */
 
@@ -65,6 +68,7 @@ int lsx_hip_poison_lds(int32_t device, int32_t rounds);
 #endif
 
 #include "lsx_hip_rates.h"
+#include "lsx_hip_losses.h"
 #include "lsx_hip_depth.h"
 #include "lsx_hip_ng.h"
 #include "lsx_hip_spectrum.h"

@@ -219,6 +219,15 @@ class LsxLibrary:
             d.lsx_hip_radiative_rates.restype = C.c_int
             d.lsx_hip_radiative_rates_work_cap.argtypes = [C.c_void_p, C.c_size_t]
             d.lsx_hip_radiative_rates_work_cap.restype = C.c_int
+        self.has_radiative_losses = hasattr(d, 'lsx_hip_radiative_losses')      # include/lsx_hip_losses.h
+        if self.has_radiative_losses:
+            d.lsx_hip_radiative_losses.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp,
+                                                   C.c_size_t, C.c_size_t, C.c_size_t]
+            d.lsx_hip_radiative_losses.restype = C.c_int
+            d.lsx_hip_radiative_losses_work_cap.argtypes = [C.c_void_p, C.c_size_t]
+            d.lsx_hip_radiative_losses_work_cap.restype = C.c_int
+            d.lsx_hip_frequency_weights.argtypes = [C.c_int32, _dp, _dp]
+            d.lsx_hip_frequency_weights.restype = C.c_int
         self.has_depth_rays = hasattr(d, 'lsx_hip_depth_rays')         # include/lsx_hip_depth.h
         if self.has_depth_rays:
             d.lsx_hip_depth_rays.argtypes = [C.c_void_p, C.c_int32, _dp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,

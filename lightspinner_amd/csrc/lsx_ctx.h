@@ -138,6 +138,13 @@ struct lsx_ctx : lsxd::LsxPlan {        // the plan (lsx_plan.h: dimensions, tab
     char* d_rates_ent = nullptr;
     double* d_rates_work = nullptr;
     size_t rates_work_doubles = 0, rates_work_cap = 0;      // cap 0: the default of include/lsx_hip_rates.h
+    // ... and of lsx_hip_radiative_losses (lsx_losses.hip): its own tables, the weights of a call (losses_wnu: the trapezoid rule in
+    // frequency over the merged grid, the default) and the pass's work arrays (allocated at first use, under losses_work_cap bytes)
+    int32_t *d_losses_ptr = nullptr, *d_losses_tile = nullptr, *d_losses_row = nullptr;
+    char* d_losses_ent = nullptr;
+    double *d_losses_work = nullptr, *d_losses_wnu = nullptr;
+    std::vector<double> losses_wnu;
+    size_t losses_work_doubles = 0, losses_work_cap = 0;    // cap 0: the default of include/lsx_hip_losses.h
     // ... and of lsx_hip_depth_rays (lsx_depth.hip), with the arrays of a pass (allocated at first use, under depth_work_cap bytes)
     int32_t *d_depth_ptr = nullptr, *d_depth_tile = nullptr;
     char* d_depth_ent = nullptr;

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/lsx.h"
+#include "../../include/lsx_hip_losses.h"
 
 namespace lsxd {
 int fail(int code, const char* fmt, ...);
@@ -181,5 +182,21 @@ extern "C" int lsx_continuum_alpha(const lsx_continuum_model* c, int32_t n, cons
             alpha[q] = (y[hi] - y[lo]) / (x[hi] - x[lo]) * (w - x[lo]) + y[lo];
         }
     }
+    return LSX_OK;
+}
+
+// the trapezoid rule in frequency over an ascending wavelength grid [nm] -> weights in Hz (include/lsx_hip_losses.h): nu = c / lambda,
+// wnu[la] = |nu[la - 1] - nu[la + 1]| / 2, half intervals at the two ends
+extern "C" int lsx_hip_frequency_weights(int32_t Nspect, const double* wavelength, double* wnu)
+{
+    if (Nspect < 1 || !wavelength || !wnu) return fail(LSX_EINVAL, "lsx_hip_frequency_weights: bad arguments");
+    for (int la = 0; la < Nspect; ++la)
+        if (!(wavelength[la] > 0.0) || (la && !(wavelength[la] > wavelength[la - 1])))
+            return fail(LSX_EINVAL, "lsx_hip_frequency_weights: wavelengths must be positive and ascend strictly");
+    auto nu = [&](int la) { return kCLight / (wavelength[la] * kNM); };
+    if (Nspect == 1) { wnu[0] = 0.0; return LSX_OK; }
+    wnu[0] = 0.5 * std::fabs(nu(0) - nu(1));
+    wnu[Nspect - 1] = 0.5 * std::fabs(nu(Nspect - 2) - nu(Nspect - 1));
+    for (int la = 1; la + 1 < Nspect; ++la) wnu[la] = 0.5 * std::fabs(nu(la - 1) - nu(la + 1));
     return LSX_OK;
 }

@@ -1311,6 +1311,7 @@ void lsx_destroy(lsx_ctx* c)
                     c->d_sa_atoms, c->d_sa_lines, c->d_sa_colls, c->d_sa_spl, c->d_sa_levE, c->d_sa_levg, c->d_sa_levnD, c->d_sa_levdZ,
                     c->d_vBroad, c->d_aDamp, c->d_vlos, c->d_prof_kind, c->d_rays_ptr, c->d_rays_tile, c->d_rays_ent,
                     c->d_rates_ptr, c->d_rates_tile, c->d_rates_row, c->d_rates_ent, c->d_rates_work,
+                    c->d_losses_ptr, c->d_losses_tile, c->d_losses_row, c->d_losses_ent, c->d_losses_work, c->d_losses_wnu,
                     c->d_depth_ptr, c->d_depth_tile, c->d_depth_ent, c->d_depth_work, c->d_spec_tab, c->d_spec_work};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);

@@ -194,6 +194,49 @@ class RadiativeRates:
         return out
 
 
+class RadiativeLosses:
+    """What Engine.radiative_losses returns (definitions, units and signs: include/lsx_hip_losses.h); an array that was not asked
+    for is None:
+      .F   [ncol][Nspace]            radiative flux, W m^-2, positive towards the observer
+      .Q   [ncol][Nspace]            net radiative cooling, W m^-3: positive means the gas loses energy
+      .Qt  [ncol][Ntrans][Nspace]    the cooling of each transition, W m^-3, the photon energy inside the wavelength sum
+      .H, .D  [ncol][Nspect][Nspace] the monochromatic Eddington flux and net emission per steradian
+      .wnu [Nspect]                  the frequency weights F and Q were summed with, Hz
+    Context.compute_losses drops the column axis and adds .transitions, the matching objects in the order of Qt."""
+    FIELDS = ('F', 'Q', 'Qt', 'H', 'D')
+
+    def __init__(self, wnu, F=None, Q=None, Qt=None, H=None, D=None, transitions=None):
+        self.wnu = wnu
+        self.F, self.Q, self.Qt, self.H, self.D = F, Q, Qt, H, D
+        self.transitions = transitions
+
+    def total(self):
+        """sum over the transitions of Qt: the cooling by the active transitions alone (Q also holds the background's share and is
+        summed with wnu, Qt with each transition's own weights)"""
+        if self.Qt is None:
+            raise ValueError("total() needs Qt: ask for it (what=('Qt', ...))")
+        return self.Qt.sum(axis=-2)
+
+    def by_transition(self, names):
+        """Qt of the named transitions -> {name: [..][Nspace]}.  A name is a place in the order of Qt, one of .transitions (the
+        object itself), or that object's .name where it has one"""
+        if self.Qt is None:
+            raise ValueError("by_transition() needs Qt: ask for it (what=('Qt', ...))")
+        out = {}
+        for name in ([names] if isinstance(names, (str, int, np.integer)) else list(names)):
+            if isinstance(name, (int, np.integer)):
+                kr = int(name)
+            elif self.transitions is None:
+                raise ValueError('by_transition() needs the transitions for %r: use Context.compute_losses()' % (name,))
+            else:
+                hits = [q for q, t in enumerate(self.transitions) if t is name or getattr(t, 'name', None) == name]
+                if len(hits) != 1:
+                    raise KeyError('%r names %d of the transitions' % (name, len(hits)))
+                kr = hits[0]
+            out[name] = self.Qt[..., kr, :]
+        return out
+
+
 class DepthRays:
     """What Engine.depth_rays returns: .chi, .S, .tau, .I, .contrib, each [ncol][nmu][Nspace][nla] (the wavelength runs fastest), and
     .z_tau1 [ncol][nmu][nla], for the up-going rays with direction cosines .mus and the wavelengths [.la0, .la0 + nla) of the merged
@@ -528,6 +571,46 @@ class Engine:
         Rij, Rji, Rji_ref = (np.empty(shape, dtype=np.float64) for _ in range(3))
         self.lib.check(self.lib.dll.lsx_hip_radiative_rates(self._h, int(col0), ncol, _ptr(Rij), _ptr(Rji), _ptr(Rji_ref), Rij.nbytes))
         return RadiativeRates(Rij, Rji, Rji_ref)
+
+    def frequency_weights(self):
+        """the weights radiative_losses uses by default: the trapezoid rule in frequency over the merged grid, [Nspect] in Hz
+        (lsx_hip_frequency_weights, formed in the library's grid code)"""
+        if not getattr(self.lib, 'has_radiative_losses', False):
+            raise NotImplementedError('%s (%s) does not export lsx_hip_frequency_weights' % (self.lib.path, self.lib.backend))
+        lam = f64(self.problem.wavelength)
+        w = np.empty_like(lam)
+        self.lib.check(self.lib.dll.lsx_hip_frequency_weights(lam.shape[0], _ptr(lam), _ptr(w)))
+        return w
+
+    def radiative_losses(self, col0=0, ncol=None, wnu=None, what=('F', 'Q', 'Qt'), work_cap_bytes=None):
+        """What the radiation does to the gas, from what the engine holds (include/lsx_hip_losses.h, lsx_hip_radiative_losses): one
+        formal solution over the engine's own rays from the current populations and J, for columns [col0, col0 + ncol).
+        -> RadiativeLosses with the arrays named in `what`, of 'F' (flux, W m^-2, positive outwards), 'Q' (net cooling, W m^-3,
+        positive: the gas loses energy), 'Qt' (per transition), 'H', 'D' (monochromatic), and .wnu, the weights used.
+        wnu: [Nspect] frequency weights in Hz for F and Q (None: the trapezoid rule over the merged grid); zeros outside a band give
+        the band's share.  work_cap_bytes: the cap of the pass's device work memory from this call on (None: unchanged; 0: the
+        default).  Read-only.  Only the HIP library computes it; there is no host version."""
+        if not getattr(self.lib, 'has_radiative_losses', False):
+            raise NotImplementedError('%s (%s) does not export lsx_hip_radiative_losses: radiative losses are computed by the HIP '
+                                      'library only' % (self.lib.path, self.lib.backend))
+        what = (what,) if isinstance(what, str) else tuple(what)
+        unknown = [w for w in what if w not in RadiativeLosses.FIELDS]
+        if unknown:
+            raise ValueError('radiative_losses: unknown array(s) %s; there are %s' % (unknown, ', '.join(RadiativeLosses.FIELDS)))
+        if work_cap_bytes is not None:
+            self.lib.check(self.lib.dll.lsx_hip_radiative_losses_work_cap(self._h, int(work_cap_bytes)))
+        p = self.problem
+        ncol = self.ncol - int(col0) if ncol is None else int(ncol)
+        nc = max(ncol, 0)
+        shapes = {'F': (nc, p.Nspace), 'Q': (nc, p.Nspace), 'Qt': (nc, p.Ntrans, p.Nspace), 'H': (nc, p.Nspect, p.Nspace),
+                  'D': (nc, p.Nspect, p.Nspace)}
+        out = {w: np.empty(shapes[w], dtype=np.float64) for w in what}
+        weights = self.frequency_weights() if wnu is None else f64(wnu, (p.Nspect,))
+        ptr = [_ptr(out[w]) if w in out else None for w in RadiativeLosses.FIELDS]
+        nbytes = [int(np.prod(shapes[w])) * 8 for w in ('F', 'Qt', 'H')]
+        self.lib.check(self.lib.dll.lsx_hip_radiative_losses(self._h, int(col0), ncol, None if wnu is None else _ptr(weights), *ptr,
+                                                             *nbytes))
+        return RadiativeLosses(weights, **out)
 
     def depth_rays(self, mus, la0=0, nla=None, col0=0, ncol=None, what=DepthRays.FIELDS, work_cap_bytes=None):
         """Opacity, source function, optical depth, intensity and contribution function at every depth along the up-going rays with

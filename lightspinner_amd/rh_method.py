@@ -55,7 +55,7 @@ import numpy as np
 
 from . import _capi, atomdata
 from . import constants as Const
-from .problem import Problem, Transition, ColumnBlock, Engine, RadiativeRates, DepthRays
+from .problem import Problem, Transition, ColumnBlock, Engine, RadiativeRates, RadiativeLosses, DepthRays
 from .spectrum import continuum_alpha
 
 _KNOWN_COLLISIONS = ('Omega', 'CI', 'CE')
@@ -503,6 +503,27 @@ class Context:
         trans = [t for a in self.activeAtoms for t in a.trans]
         pops = [(np.array(t.atom.n[t.i], dtype=np.float64), np.array(t.atom.n[t.j], dtype=np.float64)) for t in trans]
         return RadiativeRates(r.Rij[0], r.Rji[0], r.Rji_ref[0], transitions=trans, populations=pops)
+
+    def compute_losses(self, wavelength_band=None, what=('F', 'Q', 'Qt')):
+        """What the radiation does to the gas, as ONE formal solution gives it from these populations and this J
+        (include/lsx_hip_losses.h): -> an object with .F [Nspace], the radiative flux in W m^-2 (positive towards the observer),
+        .Q [Nspace], the net radiative cooling in W m^-3 (positive: the gas loses energy; dF/dz = Q), .Qt [Ntrans][Nspace], the
+        cooling of each transition in the order of `.transitions` ([t for atom in activeAtoms for t in atom.trans]) with
+        .total() and .by_transition(names), and .wnu, the frequency weights used.  wavelength_band: (lo, hi) in nm restricts F and
+        Q to the wavelengths lo <= lambda <= hi of spect.wavelength (the trapezoid weights, zeroed outside); Qt is summed over
+        each transition's own wavelengths either way.  `what` may add 'H' and 'D', the monochromatic sums [Nspect][Nspace].
+        F and Q are only as bolometric as spect.wavelength is.  Nothing of the context changes."""
+        self._cancel_lookahead()                  # (the library's J is the last accepted call's again)
+        self._push_host_edits()
+        wnu = None
+        if wavelength_band is not None:
+            lo, hi = (float(x) for x in wavelength_band)
+            lam = np.asarray(self.spect.wavelength, dtype=np.float64)
+            wnu = np.where((lam >= lo) & (lam <= hi), self._engine.frequency_weights(), 0.0)
+        r = self._engine.radiative_losses(wnu=wnu, what=what)
+        trans = [t for a in self.activeAtoms for t in a.trans]
+        return RadiativeLosses(r.wnu, transitions=trans,
+                               **{w: getattr(r, w)[0] for w in RadiativeLosses.FIELDS if getattr(r, w) is not None})
 
     def stat_equil(self) -> float:
         """rh_method.py:710-745 -> max relative population change; populations are written back IN
