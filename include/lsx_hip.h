@@ -14,7 +14,7 @@ extern "C" {
  * offers through Atmosphere.rays(mu) (atmosphere.py:386-393) followed by one formal_sol_gamma_matrices().
  * For columns [col0, col0 + ncol) and the nmu direction cosines mu[] (each in (0, 1], any nmu >= 1 -- not bound by the ray limit
  * of a context) it computes the intensity that leaves the top of the atmosphere, I(lambda, mu):
- *   - up-going rays only, thermalised lower boundary (formal_solver.py:203-207), the recurrence and its end-point quirk as the
+ *   - up-going rays only, thermalised lower boundary (formal_solver.py:203-207; ZERO where lsx_hip_set_boundary set it, GIVEN is refused: lsx_hip_boundary.h), the recurrence and its end-point quirk as the
  *     sweeps have them (formal_solver.py:46-142; emergent value I[0], rh_method.py:638); the context's rule (lsx_set_formal_solver);
  *   - opacity, emissivity and source function as rh_method.py:599-632 from the CURRENT populations (LSX_N), the background and
  *     the scattering term sigma J, where J is what lsx_get(LSX_J) would return at this moment;
@@ -55,6 +55,9 @@ int lsx_hip_emergent_rays(lsx_ctx* ctx, int32_t nmu, const double* mu, int32_t c
 /* Time-dependent populations -- an implicit step of the rate equation dn/dt = Gamma n in the place of the statistical
  * equilibrium: lsx_hip_timedep.h, included below. */
 
+/* Radiation boundary conditions at both ends of a column -- zero, thermalised or given, per column: lsx_hip_boundary.h, included
+ * below. */
+
 /* Launch counters of the kernels behind the sweep (introspection for the tests): lsx_hip_epilogue.h, included below. */
 
 /* GPU_MAX_HW_QUEUES=n for this process unless the caller has set it: call before the first HIP call. */
@@ -77,5 +80,6 @@ int lsx_hip_poison_lds(int32_t device, int32_t rounds);
 #include "lsx_hip_eqpops.h"
 #include "lsx_hip_timedep.h"
 #include "lsx_hip_epilogue.h"
+#include "lsx_hip_boundary.h"
 
 #endif /* LSX_HIP_H */

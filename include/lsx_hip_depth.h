@@ -22,7 +22,7 @@ extern "C" {
  *   tau[k]         tau[0] = 0, tau[k] = tau[k-1] + 0.5 (chi[k-1] + chi[k]) (1 / mu) |z[k-1] - z[k]|: the dtau of formal_solver.py:129
  *                  summed from the top in index order.
  *   I[k]           the up-going intensity at every depth under the context's rule (lsx_set_formal_solver): thermalised lower
- *                  boundary (formal_solver.py:203-207; I[Nspace-1] is that value), the recurrence and its end-point quirk
+ *                  boundary (formal_solver.py:203-207; I[Nspace-1] is that value; 0 where lsx_hip_set_boundary set ZERO, GIVEN is refused), the recurrence and its end-point quirk
  *                  (formal_solver.py:46-142).  I[0] is what lsx_hip_emergent_rays returns, to rounding.
  *   contrib[k]     chi[k] S[k] exp(-tau[k]) / mu: the contribution function to the emergent intensity per unit height.  It
  *                  underflows to 0 at large tau.

@@ -15,8 +15,9 @@ extern "C" {
  *   - the rays are the context's own muz / wmu, both directions, under the context's rule (lsx_set_formal_solver);
  *   - opacity and emissivity as rh_method.py:599-632 from the CURRENT populations (LSX_N), the background and the scattering term
  *     sigma J, where J is what lsx_get(LSX_J) would return at this moment;
- *   - the recurrence is the sweeps': boundary values 0 at the top and thermalised at the bottom (formal_solver.py:203-209), the
- *     end-point quirk (formal_solver.py:138-139);
+ *   - the recurrence is the sweeps': boundary values 0 at the top and thermalised at the bottom (formal_solver.py:203-209) unless
+ *     lsx_hip_set_boundary has set others for the column (lsx_hip_boundary.h: all three kinds at both ends), the end-point quirk
+ *     (formal_solver.py:138-139);
  *   - line profiles are the context's own, of every ray and both directions, whichever entry set them: nothing is re-evaluated.
  * Per wavelength la of the merged grid, depth k, ray m and direction d, with
  *   chi = sum_t (n_i Vij - n_j Vji) + chi_bg,   eta = sum_t n_j Uji + eta_bg + sigma J,   I = the recurrence's value at depth k

@@ -14,7 +14,7 @@ extern "C" {
  *   - the rays are the context's own muz / wmu, both directions, under the context's rule (lsx_set_formal_solver);
  *   - opacity, emissivity and source function as rh_method.py:599-632 from the CURRENT populations (LSX_N), the background and
  *     the scattering term sigma J, where J is what lsx_get(LSX_J) would return at this moment;
- *   - the recurrence is the sweeps': its boundary values (0 at the top, thermalised at the bottom, formal_solver.py:203-209) and
+ *   - the recurrence is the sweeps': its boundary values (0 at the top, thermalised at the bottom, formal_solver.py:203-209; or what lsx_hip_set_boundary set, lsx_hip_boundary.h) and
  *     its end-point quirk (formal_solver.py:138-139);
  *   - wlamu = wla (wmu / 2) 4 pi as rh_method.py:661-665, wla as rh_method.py:425-455;
  *   - line profiles are the context's own, of every ray and both directions, whichever entry set them (lsx_set_columns with

@@ -15,7 +15,7 @@ extern "C" {
  * any nmu >= 1) and columns [col0, col0 + ncol): what the reference offers through
  * RadiativeSet.compute_wavelength_grid(extraWavelengths=...) (atomic_set.py:377-383), a Context on the finer grid that holds these
  * populations, and one formal_sol_gamma_matrices().  No second context, no second upload of the columns.
- *   - Up-going rays only, thermalised lower boundary (formal_solver.py:203-207), the recurrence and its end-point quirk
+ *   - Up-going rays only, thermalised lower boundary (formal_solver.py:203-207; ZERO where lsx_hip_set_boundary set it, GIVEN is refused: lsx_hip_boundary.h), the recurrence and its end-point quirk
  *     (formal_solver.py:46-142; emergent value I[0], rh_method.py:638), under the context's rule (lsx_set_formal_solver), as
  *     lsx_hip_emergent_rays has them.  Planck function and Boltzmann factor are taken at the new wavelength.
  *   - Active set.  Transition kr, whose window in the context's grid lambda is [Nblue, Nblue + Nlambda), is active at lambda' iff

@@ -276,6 +276,12 @@ class LsxLibrary:
             d.lsx_hip_time_dep_update.restype = C.c_int
             d.lsx_hip_time_dep_state.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _dp, _dp]
             d.lsx_hip_time_dep_state.restype = C.c_int
+        self.has_boundary = hasattr(d, 'lsx_hip_set_boundary')         # include/lsx_hip_boundary.h
+        if self.has_boundary:
+            d.lsx_hip_set_boundary.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, _dp]
+            d.lsx_hip_set_boundary.restype = C.c_int
+            d.lsx_hip_boundary_state.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
+            d.lsx_hip_boundary_state.restype = C.c_int
         self.has_epilogue_info = hasattr(d, 'lsx_hip_epilogue_info')   # include/lsx_hip_epilogue.h
         if self.has_epilogue_info:
             d.lsx_hip_epilogue_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]

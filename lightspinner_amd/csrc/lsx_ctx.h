@@ -166,6 +166,10 @@ struct lsx_ctx : lsxd::LsxPlan {        // the plan (lsx_plan.h: dimensions, tab
     double* d_td_n_prev = nullptr;       // [col][NLtot][k]: the populations at the start of the column's time step
     double* d_td_dt = nullptr;           // [col]: the time step, 0 = no step started
     std::vector<double> td_dt;           // host copy of d_td_dt
+    // the radiation boundary (lsx_boundary.hip, include/lsx_hip_boundary.h): nothing until lsx_hip_set_boundary is first called
+    int32_t* d_bnd = nullptr;            // the boundary store (lsx_dev.h): what the kernels test: null = the hard-wired pair, code as it was
+    bool bnd_values = false;             // ... holds the start values too (re-allocated with them at the first GIVEN)
+    std::vector<int32_t> bnd_kind;       // host copy of the kinds in the store, [col][2] = (lower, upper) (empty: never set)
     // staging
     double* d_stage = nullptr;
     size_t stage_doubles = 0;
@@ -237,5 +241,6 @@ int ng_enqueue(lsx_ctx* c);                              // the step behind a st
 int ng_reset(lsx_ctx* c, size_t col0, size_t ncol);      // these columns' populations have been replaced: their history is discarded
 void ng_free(lsx_ctx* c);
 void td_free(lsx_ctx* c);                                // the state of the time-dependent step (lsx_timedep.hip)
+void boundary_free(lsx_ctx* c);                          // the radiation boundary (lsx_boundary.hip)
 
 } // namespace lsxd

@@ -66,6 +66,7 @@ struct DepthParams {
     const double *aDamp, *vBroad, *vlos;
     const uint8_t* prof_kind;   // per column: 2 = profiles built by the library with a line-of-sight velocity (ray dependent)
     double *chi, *S, *tau, *I, *contrib;    // each [launch column][nmu][Ns][nla]
+    const int32_t* bnd;         // the radiation boundary (lsx_dev.h, the boundary store), or null
     double* ztau1;              // [launch column][nmu][nla]
 };
 
@@ -94,6 +95,8 @@ __global__ void __launch_bounds__(64) k_depth_rays(const DepthParams p)
     const int q = valid ? q_raw : p.nla - 1;               // every lane walks a wavelength (w2 / w3 are wave-wide); spare ones store nothing
     const int la = p.la0 + q;
     const size_t col = (size_t)p.col0 + blockIdx.y;
+    // the lower boundary (include/lsx_hip_boundary.h): thermalised unless the column has been given ZERO (GIVEN is refused on the host)
+    const bool lower_zero = p.bnd != nullptr && boundary_kind(p.bnd, col, LSX_BND_LOWER) == 0;
     const int tile = p.la_tile[2 * la], j = p.la_tile[2 * la + 1];
     const size_t toff = (size_t)tile * Ns * L + j;         // + k L: this wavelength in a tile-major stream
     const double* __restrict__ bgchi = p.bgchi_T + col * p.til_col + toff;
@@ -246,7 +249,7 @@ __global__ void __launch_bounds__(64) k_depth_rays(const DepthParams p)
                 }
                 if (s == 1) {                                      // thermalised lower boundary, formal_solver.py:203-207
                     const double dtau_uw = zmu[m] * (c_k[m] + chi[m]) * 0.5 * adz;
-                    Iu[m] = B1 - (B0 - B1) / dtau_uw;
+                    Iu[m] = lower_zero ? 0.0 : B1 - (B0 - B1) / dtau_uw;
                     if (valid) o_I[((size_t)m * Ns + k + 1) * p.nla] = Iu[m];        // I[kStart] = Istart, :117
                 }
                 const double dtau = 0.5 * (c_k[m] + chi[m]) * zmu[m] * adz;         // :107, :129
@@ -271,7 +274,7 @@ __global__ void __launch_bounds__(64) k_depth_rays(const DepthParams p)
                 const double c_d = chi[m], S_d = Sd[m];
                 if (s == 1) {
                     const double dtau_uw = zmu[m] * (c_k[m] + c_d) * 0.5 * fabs(zk1 - zk);
-                    Iu[m] = B1 - (B0 - B1) / dtau_uw;
+                    Iu[m] = lower_zero ? 0.0 : B1 - (B0 - B1) / dtau_uw;
                     if (valid) o_I[((size_t)m * Ns + k + 1) * p.nla] = Iu[m];
                 }
                 if (s >= 2) {
@@ -389,6 +392,9 @@ extern "C" int lsx_hip_depth_rays(lsx_ctx* c, int32_t nmu, const double* mu, int
     if (z_tau1 && nbytes_z != (size_t)ncol * zper * 8) return fail(LSX_EINVAL, "lsx_hip_depth_rays: nbytes_z does not match [ncol][nmu][nla]");
     if (c->Nspace < 3) return fail(LSX_EUNSUPPORTED, "lsx_hip_depth_rays: needs Nspace >= 3");
     for (int q = col0; q < col0 + ncol; ++q) {
+        if (!c->bnd_kind.empty() && c->bnd_kind[2 * (size_t)q] == LSX_BOUNDARY_GIVEN)
+            return fail(LSX_EUNSUPPORTED, "lsx_hip_depth_rays: column %d has a GIVEN lower boundary (lsx_hip_set_boundary): its intensity was handed "
+                                          "over on the context's own rays and wavelengths and is not known at another angle", q);
         if (!c->phi_set[q])
             return fail(LSX_EINVAL, "lsx_hip_depth_rays: column %d has no line profiles (lsx_set_columns with phi == NULL must be "
                                     "followed by lsx_set_line_profiles)", q);
@@ -426,6 +432,7 @@ extern "C" int lsx_hip_depth_rays(lsx_ctx* c, int32_t nmu, const double* mu, int
     p.wavelength = c->d_wavelength; p.u_la = c->d_u_la; p.exp2_tab = c->d_exp2_tab; p.voigt_W = c->d_voigt_w; p.mu = d_mu;
     p.la_ptr = c->d_depth_ptr; p.ents = reinterpret_cast<const DepthEnt*>(c->d_depth_ent); p.la_tile = c->d_depth_tile;
     p.height = c->d_height; p.temperature = c->d_temperature; p.n = c->d_n; p.nsr = c->d_nsr;
+    p.bnd = c->d_bnd;
     p.bgchi_T = c->d_bgchi; p.bgeta_T = c->d_bgeta; p.J_T = c->d_J[c->jcur];      // what lsx_get(LSX_J) returns at this moment
     p.E_T = c->d_E; p.sca = c->d_sca; p.phi_T = c->d_phi;
     p.aDamp = c->d_aDamp; p.vBroad = c->d_vBroad; p.vlos = c->d_vlos; p.prof_kind = c->d_prof_kind;

@@ -175,7 +175,39 @@ struct SweepParams {
     const int32_t* trans_row;   // per transition: its row of wphi (lines) / its continuum index (continua)
     int32_t fold, fold_nF;      // the launched class runs its FOLDED instance (lsx_plan.h); the most fast continua a tile of it has
     int32_t epi, pad_epi;       // ... its EPI instance: the second visitor of a depth forms the fast continua's Gamma integrands itself
+    // radiation boundary (include/lsx_hip_boundary.h): null = the hard-wired pair (thermalised below, zero above) through the code as
+    // it was; else the context's boundary store (below).  ONE pointer: the final passes' parameter blocks fill the scalar registers,
+    // and every further argument is one more spill
+    const int32_t* bnd;
 };
+
+// ---- the boundary store: one device allocation, int32 header {ncol of the context, 1 if the start values follow, 0, 0}, the kinds
+// [ncol][2] = (lower, upper), then -- once a column has a GIVEN end -- the start values [end: 0 lower, 1 upper][ncol][Nspect][Nrays]
+// as doubles (16 + 8 ncol bytes in: aligned)
+#define LSX_BND_HEADER 4
+#define LSX_BND_LOWER 0
+#define LSX_BND_UPPER 1
+static inline size_t boundary_store_bytes(size_t ncol, size_t per, bool with_values)
+{
+    return (LSX_BND_HEADER + 2 * ncol) * sizeof(int32_t) + (with_values ? 2 * ncol * per * sizeof(double) : 0);
+}
+#ifdef __HIPCC__
+static __device__ __forceinline__ int boundary_kind(const int32_t* b, size_t col, int end) { return b[LSX_BND_HEADER + 2 * col + end]; }
+// the start values of (end, column): [Nspect][Nrays], per = Nspect * Nrays; only dereferenced where the kind is GIVEN
+static __device__ __forceinline__ const double* boundary_given(const int32_t* b, int end, size_t col, size_t per)
+{
+    const size_t nc = (size_t)b[0];
+    return reinterpret_cast<const double*>(b + LSX_BND_HEADER + 2 * nc) + ((size_t)end * nc + col) * per;
+}
+// the start value of a ray from its end's kind: `therm` is the thermalised value of that end, `given` points at the ray's entry of
+// the handed-over intensities and is read only where the kind asks for it
+static __device__ __forceinline__ double boundary_start(int kind, double therm, const double* given)
+{
+    double v = kind == 1 ? therm : 0.0;
+    if (kind == 2) v = *given;
+    return v;
+}
+#endif
 
 // ---- the line-profile store phi_T --------------------------------------------------------------------------------------------
 // Per (tile, line) block and column the profile is [dir][k][mu][l < len] (x = (dir Nspace + k) Nrays + mu is the block's row; compact

@@ -1338,6 +1338,7 @@ void lsx_destroy(lsx_ctx* c)
     if (c->h_n) (void)hipHostFree(c->h_n);
     ng_free(c);
     td_free(c);
+    boundary_free(c);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -1777,6 +1778,7 @@ static int enqueue_fs(lsx_ctx* c, bool timed, bool speculative = false)
     p.bgchi_T = c->d_bgchi; p.bgeta_T = c->d_bgeta; p.bgce_T = c->d_bgce; p.bgxce_T = c->d_bgxce; p.bgxchi_T = c->d_bgxchi; p.bgxeta_T = c->d_bgxeta; p.Psi2_T = c->d_Psi2; p.sca = c->d_sca; p.phi_T = c->d_phi; p.nsr = c->d_nsr; p.Ncont = c->Ncont; p.E_T = c->d_E; p.corr_T = c->d_corr; p.Psi3_T = c->d_Psi3;
     p.Jdag_T = c->d_J[c->jcur]; p.Jnew_T = c->d_J[c->jcur ^ 1];
     p.Iout = c->d_I; p.Gpart = c->d_Gpart; p.dJpart = c->d_dJpart; p.debug = c->d_debug; p.colmask = c->d_colmask; p.exp2_tab = c->d_exp2_tab; p.static_max = c->static_max;
+    p.bnd = c->d_bnd;      // (lsx_hip_set_boundary drops the captured graphs: this is a kernel argument)
 
     FastParams ff{};
     const bool has_fast = !c->fast_tiles.empty();

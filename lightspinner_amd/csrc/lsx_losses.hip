@@ -70,6 +70,7 @@ struct LossParams {
     double *Hw, *Dw, *Jp;       // work: [launch column][k][Nspect] each
     double2* PP;                // work: [launch column][k][SNl] (P, Phi)
     double wsum;                // sum of wmu / 2 over rays and directions
+    const int32_t* bnd;         // the radiation boundary (lsx_dev.h, the boundary store): null = thermalised below, zero above, as it was
     double *F, *Q, *Qt, *Ht, *Dt;   // device results of a pass: [launch column][k], [launch column][Ntrans][k], [launch column][Nspect][k]
 };
 
@@ -82,8 +83,16 @@ __device__ __forceinline__ double planck(double temp, double wav)
     return twohnu3_c2 / (exp(hc_Tkla) - 1.0);
 }
 
+// waves per SIMD of the pass's instances by rays per lane, as DESIGN.md 4.19 states them: asked of the compiler, so that the boundary's
+// arm of the start values moves no instance to another count.  What holds this table, the one in DESIGN.md and the
+// compiler together is tests/test_radiative_losses_host.py: it reads every instance's waves per SIMD from the compiler's report and compares
+// them with the same table (a count the allocator cannot reach shows there as another count or as scratch)
+constexpr int losses_waves(int nm, bool par) { return nm == 1 ? (par ? 4 : 5) : nm == 2 ? (par ? 3 : 4) : nm == 3 ? 3 : nm == 4 ? (par ? 2 : 3) : 2; }
+static_assert(losses_waves(1, false) >= losses_waves(5, false) && losses_waves(5, true) == 2, "more rays per lane never means more waves; five rays: two");
+
 template <int NM, bool PAR>
-__global__ void __launch_bounds__(64) k_losses_pass(const LossParams p)
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(losses_waves(NM, PAR), losses_waves(NM, PAR))))
+k_losses_pass(const LossParams p)
 {
     __shared__ double etab_s[LSX_EXP_TAB];
     for (int e = threadIdx.x; e < LSX_EXP_TAB; e += 64) etab_s[e] = p.exp2_tab[e];
@@ -229,7 +238,29 @@ __global__ void __launch_bounds__(64) k_losses_pass(const LossParams p)
             // ---- the recurrence at this depth ----
             double B0 = 0.0, B1 = 0.0;
             if (up && s == 1) { B0 = planck(p.temperature[col * Ns + Ns - 2], wav); B1 = planck(p.temperature[col * Ns + Ns - 1], wav); }
-            if (s == 1) {                  // the value the ray starts with belongs to the depth behind: 0 at the top, thermalised at the bottom
+            if (s == 1 && p.bnd != nullptr) {
+                // a boundary has been set (include/lsx_hip_boundary.h): the kind of this direction's end of the column (wave-uniform:
+                // a block is one column); the thermalised value of the upper end is the mirror image of the lower one (k1: the end's
+                // depth, k: the next one)
+                const int end = up ? LSX_BND_LOWER : LSX_BND_UPPER;
+                const int kind = boundary_kind(p.bnd, col, end);
+                if (kind == 1) {
+                    const double Bn = planck(p.temperature[col * Ns + k], wav), Be = planck(p.temperature[col * Ns + k1], wav);
+#pragma unroll
+                    for (int m = 0; m < NM; ++m) {
+                        const double dtau_uw = zmu[m] * (c_k[m] + chi[m]) * 0.5 * fabs(zk1 - zk);
+                        Iu[m] = Be - (Bn - Be) / dtau_uw;
+                    }
+                } else if (kind == 2) {
+                    const double* given = boundary_given(p.bnd, end, col, (size_t)p.Nspect * p.Nrays) + (size_t)la * p.Nrays + p.mu0;
+#pragma unroll
+                    for (int m = 0; m < NM; ++m) Iu[m] = given[m];
+                } else {
+#pragma unroll
+                    for (int m = 0; m < NM; ++m) Iu[m] = 0.0;
+                }
+                accumulate_cs(k1, Iu, c_k, S_k);
+            } else if (s == 1) {           // the value the ray starts with belongs to the depth behind: 0 at the top, thermalised at the bottom
 #pragma unroll
                 for (int m = 0; m < NM; ++m) {
                     if (up) {
@@ -515,6 +546,7 @@ extern "C" int lsx_hip_radiative_losses(lsx_ctx* c, int32_t col0, int32_t ncol, 
     p.height = c->d_height; p.temperature = c->d_temperature; p.n = c->d_n; p.nsr = c->d_nsr; p.wphi = c->d_wphi;
     p.bgchi_T = c->d_bgchi; p.bgeta_T = c->d_bgeta; p.J_T = c->d_J[c->jcur];      // what lsx_get(LSX_J) returns at this moment
     p.E_T = c->d_E; p.sca = c->d_sca; p.phi_T = c->d_phi;
+    p.bnd = c->d_bnd;
     p.wsum = 0.0;
     for (int dir = 0; dir < 2; ++dir)
         for (int m = 0; m < c->Nrays; ++m) p.wsum += c->wmuh[m];

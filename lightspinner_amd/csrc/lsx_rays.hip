@@ -61,6 +61,7 @@ struct RaysParams {
     const double *height, *temperature, *n, *nsr, *bgchi_T, *bgeta_T, *J_T, *E_T, *sca, *phi_T;
     const double *aDamp, *vBroad, *vlos;
     const uint8_t* prof_kind;   // per column: 2 = profiles built by the library with a line-of-sight velocity (ray dependent)
+    const int32_t* bnd;         // the radiation boundary (lsx_dev.h, the boundary store), or null
     double* out;                // [launch column][Nspect][nmu]
 };
 
@@ -88,6 +89,8 @@ __global__ void __launch_bounds__(64) k_emergent_rays(const RaysParams p)
     const bool valid = la_raw < p.Nspect;
     const int la = valid ? la_raw : p.Nspect - 1;          // every lane walks a wavelength (w2 / w3 are wave-wide); spare ones store nothing
     const size_t col = (size_t)p.col0 + blockIdx.y;
+    // the lower boundary (include/lsx_hip_boundary.h): thermalised unless the column has been given ZERO (GIVEN is refused on the host)
+    const bool lower_zero = p.bnd != nullptr && boundary_kind(p.bnd, col, LSX_BND_LOWER) == 0;
     const int tile = p.la_tile[2 * la], j = p.la_tile[2 * la + 1];
     const size_t toff = (size_t)tile * Ns * L + j;         // + k L: this wavelength in a tile-major stream
     const double* __restrict__ bgchi = p.bgchi_T + col * p.til_col + toff;
@@ -177,7 +180,7 @@ __global__ void __launch_bounds__(64) k_emergent_rays(const RaysParams p)
                 }
                 if (s == 1) {                                      // thermalised lower boundary, formal_solver.py:203-207
                     const double dtau_uw = zmu[m] * (c_k[m] + chi[m]) * 0.5 * fabs(zk1 - zk);
-                    Iu[m] = B1 - (B0 - B1) / dtau_uw;
+                    Iu[m] = lower_zero ? 0.0 : B1 - (B0 - B1) / dtau_uw;
                 }
                 const double dtau = (c_k[m] + chi[m]) * (hdz * zmu[m]);
                 const double rcd = rcp(chi[m] * dtau);
@@ -204,7 +207,7 @@ __global__ void __launch_bounds__(64) k_emergent_rays(const RaysParams p)
                 const double c_d = chi[m], S_d = eta[m] / chi[m];
                 if (s == 1) {
                     const double dtau_uw = zmu[m] * (c_k[m] + c_d) * 0.5 * fabs(zk1 - zk);
-                    Iu[m] = B1 - (B0 - B1) / dtau_uw;
+                    Iu[m] = lower_zero ? 0.0 : B1 - (B0 - B1) / dtau_uw;
                 }
                 if (s >= 2) {
                     const double dtau_u = (c_u[m] + c_k[m]) * (0.5 * fabs(zk2 - zk1)) * zmu[m];
@@ -305,6 +308,9 @@ extern "C" int lsx_hip_emergent_rays(lsx_ctx* c, int32_t nmu, const double* mu, 
     if (nbytes != (size_t)ncol * per * 8) return fail(LSX_EINVAL, "lsx_hip_emergent_rays: nbytes does not match [ncol][Nspect][nmu]");
     if (c->Nspace < 3) return fail(LSX_EUNSUPPORTED, "lsx_hip_emergent_rays: needs Nspace >= 3");
     for (int q = col0; q < col0 + ncol; ++q) {
+        if (!c->bnd_kind.empty() && c->bnd_kind[2 * (size_t)q] == LSX_BOUNDARY_GIVEN)
+            return fail(LSX_EUNSUPPORTED, "lsx_hip_emergent_rays: column %d has a GIVEN lower boundary (lsx_hip_set_boundary): its intensity was handed "
+                                          "over on the context's own rays and wavelengths and is not known at another angle", q);
         if (!c->phi_set[q])
             return fail(LSX_EINVAL, "lsx_hip_emergent_rays: column %d has no line profiles (lsx_set_columns with phi == NULL must be "
                                     "followed by lsx_set_line_profiles)", q);
@@ -333,6 +339,7 @@ extern "C" int lsx_hip_emergent_rays(lsx_ctx* c, int32_t nmu, const double* mu, 
     p.wavelength = c->d_wavelength; p.u_la = c->d_u_la; p.exp2_tab = c->d_exp2_tab; p.voigt_W = c->d_voigt_w; p.mu = d_mu;
     p.la_ptr = c->d_rays_ptr; p.ents = reinterpret_cast<const RayEnt*>(c->d_rays_ent); p.la_tile = c->d_rays_tile;
     p.height = c->d_height; p.temperature = c->d_temperature; p.n = c->d_n; p.nsr = c->d_nsr;
+    p.bnd = c->d_bnd;
     p.bgchi_T = c->d_bgchi; p.bgeta_T = c->d_bgeta; p.J_T = c->d_J[c->jcur];      // what lsx_get(LSX_J) returns at this moment
     p.E_T = c->d_E; p.sca = c->d_sca; p.phi_T = c->d_phi;
     p.aDamp = c->d_aDamp; p.vBroad = c->d_vBroad; p.vlos = c->d_vlos; p.prof_kind = c->d_prof_kind;

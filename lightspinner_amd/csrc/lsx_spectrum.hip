@@ -68,6 +68,7 @@ struct SpecParams {
     const double *height, *temperature, *n, *nsr, *bgchi_T, *bgeta_T, *J_T, *sca;
     const double *aDamp, *vBroad, *vlos;
     const uint8_t* prof_kind;
+    const int32_t* bnd;         // the radiation boundary (lsx_dev.h, the boundary store), or null
     // the pass's: the caller's background, wavelength fastest ([launch column][k][nla]); the result [launch column][nla][nmu]
     const double *xchi, *xeta, *xsca;
     double* out;
@@ -125,6 +126,8 @@ __global__ void __launch_bounds__(64) k_spectrum(const SpecParams p)
     const bool valid = q_raw < p.nla;
     const int q = valid ? q_raw : p.nla - 1;               // every lane walks a wavelength (w2 / w3 are wave-wide); spare ones store nothing
     const size_t col = (size_t)p.col0 + blockIdx.y;
+    // the lower boundary (include/lsx_hip_boundary.h): thermalised unless the column has been given ZERO (GIVEN is refused on the host)
+    const bool lower_zero = p.bnd != nullptr && boundary_kind(p.bnd, col, LSX_BND_LOWER) == 0;
     const size_t o0 = (size_t)p.off0[q], o1 = (size_t)p.off1[q];
     const double tq = p.t[q];
     const double* __restrict__ bgchi = p.bgchi_T + col * p.til_col;
@@ -230,7 +233,7 @@ __global__ void __launch_bounds__(64) k_spectrum(const SpecParams p)
                 }
                 if (s == 1) {                                      // thermalised lower boundary, formal_solver.py:203-207
                     const double dtau_uw = zmu[m] * (c_k[m] + chi[m]) * 0.5 * adz;
-                    Iu[m] = B1 - (B0 - B1) / dtau_uw;
+                    Iu[m] = lower_zero ? 0.0 : B1 - (B0 - B1) / dtau_uw;
                 }
                 const double dtau = 0.5 * (c_k[m] + chi[m]) * zmu[m] * adz;         // :107, :129
                 const double dS = (S_k[m] - S) / dtau;                              // :111, :130
@@ -252,7 +255,7 @@ __global__ void __launch_bounds__(64) k_spectrum(const SpecParams p)
                 const double c_d = chi[m], S_d = eta[m] / chi[m];
                 if (s == 1) {
                     const double dtau_uw = zmu[m] * (c_k[m] + c_d) * 0.5 * fabs(zk1 - zk);
-                    Iu[m] = B1 - (B0 - B1) / dtau_uw;
+                    Iu[m] = lower_zero ? 0.0 : B1 - (B0 - B1) / dtau_uw;
                 }
                 if (s >= 2) {
                     const double dtau_u = (c_u[m] + c_k[m]) * (0.5 * fabs(zk2 - zk1)) * zmu[m];
@@ -436,6 +439,9 @@ extern "C" int lsx_hip_spectrum(lsx_ctx* c, int32_t nla, const double* wavelengt
     if (c->Ncont > 0 && !alpha) return fail(LSX_EINVAL, "lsx_hip_spectrum: alpha is NULL and the context has %d continua", c->Ncont);
     if (c->Nspace < 3) return fail(LSX_EUNSUPPORTED, "lsx_hip_spectrum: needs Nspace >= 3");
     for (int q = col0; q < col0 + ncol; ++q) {
+        if (!c->bnd_kind.empty() && c->bnd_kind[2 * (size_t)q] == LSX_BOUNDARY_GIVEN)
+            return fail(LSX_EUNSUPPORTED, "lsx_hip_spectrum: column %d has a GIVEN lower boundary (lsx_hip_set_boundary): its intensity was handed "
+                                          "over on the context's own rays and wavelengths and is not known at another angle or wavelength", q);
         if (!c->phi_set[q])
             return fail(LSX_EINVAL, "lsx_hip_spectrum: column %d has no line profiles (lsx_set_columns with phi == NULL must be "
                                     "followed by lsx_set_line_profiles)", q);
@@ -498,6 +504,7 @@ extern "C" int lsx_hip_spectrum(lsx_ctx* c, int32_t nla, const double* wavelengt
     p.ent_tid = (const int32_t*)(tb + a_tid); p.tr_i = (const int32_t*)(tb + a_tri);
     p.exp2_tab = c->d_exp2_tab; p.voigt_W = c->d_voigt_w;
     p.height = c->d_height; p.temperature = c->d_temperature; p.n = c->d_n; p.nsr = c->d_nsr;
+    p.bnd = c->d_bnd;
     p.bgchi_T = c->d_bgchi; p.bgeta_T = c->d_bgeta; p.J_T = c->d_J[c->jcur];      // what lsx_get(LSX_J) returns at this moment
     p.sca = c->d_sca;
     p.aDamp = c->d_aDamp; p.vBroad = c->d_vBroad; p.vlos = c->d_vlos; p.prof_kind = c->d_prof_kind;

@@ -332,12 +332,21 @@ __device__ __forceinline__ void sweep_tile(const SweepParams& p, const int vb, c
 
     // ---- boundary conditions: formal_solver.py:203-209 -------------------------------
     double Iu = 0.0;
-    if (dir) {
+    // a boundary that has been set (include/lsx_hip_boundary.h, p.bnd != null) asks for the kind of this wave's end of the column;
+    // the thermalised value of the upper end is the mirror image of the lower one: the same look-ahead from depth 0
+    // (with a boundary set the look-ahead is formed for either direction and whatever the kind: for ZERO and GIVEN its value -- which
+    // may be inf or NaN where the two opacities vanish -- is discarded by the select below and enters nothing)
+    const bool bset = p.bnd != nullptr;
+    if (dir || bset) {
         const double c0 = chi_at(kS), c1 = chi_at(kS + dk);
         const double dtau_uw = zmu_l * (c0 + c1) * 0.5 * fabs(z[kS] - z[kS + dk]);
-        const double B0 = planck(tcol[Ns - 2], wav);
-        const double B1 = planck(tcol[Ns - 1], wav);
+        const double B0 = planck(tcol[kS + dk], wav);
+        const double B1 = planck(tcol[kS], wav);
         Iu = B1 - (B0 - B1) / dtau_uw;
+    }
+    if (bset) {
+        const int end = dir ? LSX_BND_LOWER : LSX_BND_UPPER;
+        Iu = boundary_start(boundary_kind(p.bnd, col, end), Iu, boundary_given(p.bnd, end, col, (size_t)Nspect * Nrays) + (size_t)la * Nrays + mu);
     }
 
     double chi_prev = 1.0, S_prev = 0.0, dtau_prev = 1.0;
@@ -928,12 +937,17 @@ __device__ __forceinline__ void sweep_tile_parabolic(const SweepParams& p, const
     double Iu = 0.0;
     double c_u = 1.0, S_u = 0.0, c_k = 1.0, S_k = 0.0, c_d = 1.0, S_d = 0.0;     // upwind / local / downwind of the depth being finished
     opac(kS, false, c_d, S_d);
-    if (dir) {
+    const bool bset = p.bnd != nullptr;      // a boundary has been set (include/lsx_hip_boundary.h), as in sweep_tile
+    if (dir || bset) {
         double c1, S1;
         opac(kS + dk, false, c1, S1);
         const double dtau_uw = zmu_l * (c_d + c1) * 0.5 * fabs(z[kS] - z[kS + dk]);
-        const double B0 = planck(tcol[Ns - 2], wav), B1 = planck(tcol[Ns - 1], wav);
+        const double B0 = planck(tcol[kS + dk], wav), B1 = planck(tcol[kS], wav);
         Iu = B1 - (B0 - B1) / dtau_uw;
+    }
+    if (bset) {
+        const int end = dir ? LSX_BND_LOWER : LSX_BND_UPPER;
+        Iu = boundary_start(boundary_kind(p.bnd, col, end), Iu, boundary_given(p.bnd, end, col, (size_t)Nspect * Nrays) + (size_t)la * Nrays + mu);
     }
     double dJ = 0.0;
     auto gslot = [&](int k, int u, int e) -> double* { return gpart + ((u * 2 + e) * 2 + dir) * Ns + k; };
@@ -1219,12 +1233,17 @@ __device__ __forceinline__ void sweep_tile_par(const SweepParams& p, const int v
     stream_loads(kS + dk, sB);
     front(kS, sA, dprev);
     double Iu = 0.0;
-    if (dir) {
+    const bool bset = p.bnd != nullptr;      // a boundary has been set (include/lsx_hip_boundary.h), as in sweep_tile
+    if (dir || bset) {
         Dep d1;
         front(kS + dk, sB, d1);
         const double dtau_uw = zmu_l * (dprev.chi + d1.chi) * 0.5 * fabs(z[kS] - z[kS + dk]);
-        const double B0 = planck(tcol[Ns - 2], wav), B1 = planck(tcol[Ns - 1], wav);
+        const double B0 = planck(tcol[kS + dk], wav), B1 = planck(tcol[kS], wav);
         Iu = B1 - (B0 - B1) / dtau_uw;
+    }
+    if (bset) {
+        const int end = dir ? LSX_BND_LOWER : LSX_BND_UPPER;
+        Iu = boundary_start(boundary_kind(p.bnd, col, end), Iu, boundary_given(p.bnd, end, col, (size_t)Nspect * NR) + (size_t)la * NR + mu);
     }
     double S_u = 0.0, dtau_u = 1.0, rdt_u = 1.0;   // source function of the upwind depth, optical depth of the interval behind the local one and its reciprocal
     double dJ = 0.0;

@@ -415,7 +415,22 @@ lsx_sweep_rs_kernel(const SweepParams p)
     Ops opA, opB;
     load_ops(kS, opA);
     load_ops(kS + dk, opB);
-    if (dir) {
+    if (p.bnd != nullptr) {
+        // a boundary has been set (include/lsx_hip_boundary.h): per lane, the kind of this wave's end of the lane's column.  The
+        // thermalised value of the upper end is the mirror image of the lower one: the same two depths' operands at the other end
+        const Ops &cur = opA, &nxt = opB;
+        const auto* tcol = p.temperature + (size_t)col * Ns;
+        const double B0 = planck(tcol[kS + dk], wav), B1 = planck(tcol[kS], wav);
+        const double hz = ring_row(1)[lcg];                          // half the interval between depths kS and kS + dk, either direction
+        const int end = dir ? LSX_BND_LOWER : LSX_BND_UPPER;
+        const int kind = boundary_kind(p.bnd, col, end);
+        const double* given = boundary_given(p.bnd, end, col, (size_t)Nspect * NR) + (size_t)la * NR;     // NR consecutive doubles
+#pragma unroll
+        for (int m = 0; m < NR; ++m) {
+            const double dtau_uw = zmu(m) * (chi_of(cur, 0, m) + chi_of(nxt, 1, m)) * hz;
+            Iu[m] = boundary_start(kind, B1 - (B0 - B1) / dtau_uw, given + m);
+        }
+    } else if (dir) {
         const Ops &cur = opA, &nxt = opB;
         const auto* tcol = p.temperature + (size_t)col * Ns;
         const double B0 = planck(tcol[Ns - 2], wav), B1 = planck(tcol[Ns - 1], wav);

@@ -778,6 +778,42 @@ class Engine:
                                                      rj.ctypes.data_as(ip32), _ptr(coef)))
         return NgState(st, ap, rj, coef)
 
+    # ---- radiation boundary conditions (include/lsx_hip_boundary.h) ----
+    def set_boundary(self, lower='thermalised', upper='zero', I_lower=None, I_upper=None, col0=0, ncol=None):
+        """The boundary of columns [col0, col0 + ncol) (lsx_hip_set_boundary): what up-going rays start with at the lower end and
+        down-going rays at the upper end.  Kinds: 'zero', 'thermalised', 'given' (boundary.kind_code: strings, enum-like objects
+        with .name, the LSX_BOUNDARY_* integers), or a boundary.Boundary as `lower`.  I_lower / I_upper [ncol][Nspect][Nrays], or
+        [Nspect][Nrays] for every column of the range: needed exactly where the kind is 'given'.  Engine state: it holds for every
+        following formal solution, radiative_rates and radiative_losses until it is set again, set_columns / setup_columns do not
+        reset it; emergent_rays, depth_rays and emergent_spectrum refuse a 'given' lower boundary.  An engine on which it has
+        never been called has ('thermalised', 'zero').  Only the HIP library has it; there is no host version."""
+        from . import boundary as B
+        if not getattr(self.lib, 'has_boundary', False):
+            raise NotImplementedError('%s (%s) does not export lsx_hip_set_boundary: boundary conditions other than the '
+                                      "reference's are set in the HIP library only" % (self.lib.path, self.lib.backend))
+        if isinstance(lower, B.Boundary):
+            if I_lower is not None or I_upper is not None or B.kind_code(upper) != B.ZERO:
+                raise ValueError('set_boundary: a Boundary brings its own upper kind and arrays')
+            lower, upper, I_lower, I_upper = lower.lower, lower.upper, lower.I_lower, lower.I_upper
+        lo, up = B.kind_code(lower), B.kind_code(upper)
+        ncol = self.ncol - int(col0) if ncol is None else int(ncol)
+        shape = (self.problem.Nspect, self.problem.Nrays)
+        a_lo = B._array(I_lower, lo, 'lower', shape, max(ncol, 0))
+        a_up = B._array(I_upper, up, 'upper', shape, max(ncol, 0))
+        self.lib.check(self.lib.dll.lsx_hip_set_boundary(self._h, int(col0), ncol, lo, up, None if a_lo is None else _ptr(a_lo),
+                                                         None if a_up is None else _ptr(a_up)))
+
+    def boundary_state(self, col0=0, ncol=None):
+        """-> int32 [ncol][2]: the (lower, upper) kinds of columns [col0, col0 + ncol) (lsx_hip_boundary_state; boundary.ZERO,
+        .THERMALISED, .GIVEN)"""
+        if not getattr(self.lib, 'has_boundary', False):
+            raise NotImplementedError('%s (%s) does not export lsx_hip_boundary_state: boundary conditions other than the '
+                                      "reference's are set in the HIP library only" % (self.lib.path, self.lib.backend))
+        ncol = self.ncol - int(col0) if ncol is None else int(ncol)
+        kinds = np.zeros((max(ncol, 0), 2), dtype=np.int32)
+        self.lib.check(self.lib.dll.lsx_hip_boundary_state(self._h, int(col0), ncol, kinds.ctypes.data_as(C.POINTER(C.c_int32))))
+        return kinds
+
     # ---- time-dependent populations (include/lsx_hip_timedep.h) ----
     def _time_dep_lib(self, entry):
         if not getattr(self.lib, 'has_time_dep', False):

@@ -214,7 +214,11 @@ class Context:
     """rh_method.py:490-745 on the GPU."""
 
     def __init__(self, atmos, spect, eqPops, background, device: int = 0, stream=None, lib=None, setup: str = 'auto',
-                 formal_solver: str = 'linear', readback: str = 'lazy', lookahead: Optional[bool] = None, *, ng=None):
+                 formal_solver: str = 'linear', readback: str = 'lazy', lookahead: Optional[bool] = None, *, ng=None,
+                 boundary=None):
+        # boundary (include/lsx_hip_boundary.h): None -- the reference's hard-wired pair (thermalised below, zero above): the
+        # reference ignores atmos.lowerBc / upperBc, and a drop-in gives the reference's numbers for the reference's inputs; no call
+        # to the setter is made.  'atmos': the kinds the atmosphere carries.  A boundary.Boundary: applied as given.
         self.atmos = atmos
         self.atmos.nondimensionalise()
         self.spect = spect
@@ -268,6 +272,16 @@ class Context:
             self._engine.set_formal_solver(formal_solver)
         if ng is not None and ng.order:         # problem.NgOptions: Ng acceleration behind every stat_equil (include/lsx_hip_ng.h)
             self._engine.configure_ng(ng)
+        if boundary is not None:
+            from .boundary import Boundary
+            if isinstance(boundary, str):
+                if boundary != 'atmos':
+                    raise ValueError("boundary must be None, 'atmos' or a boundary.Boundary")
+                boundary = Boundary.from_atmos(atmos)
+            elif not isinstance(boundary, Boundary):
+                raise ValueError("boundary must be None, 'atmos' or a boundary.Boundary")
+            self._engine.set_boundary(boundary)
+        self.boundary = boundary
         self._cache = {}
         if setup == 'native':
             in_table = lambda m, l: _contains(spect.transitions, l)
