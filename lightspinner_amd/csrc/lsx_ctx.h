@@ -16,6 +16,7 @@
 namespace lsxd {
 extern thread_local std::string g_err;
 int fail(int code, const char* fmt, ...);    // records the message lsx_last_error returns; -> code
+struct FinalEnt;                             // an entry of the final passes' tables (lsx_final_dev.h)
 } // namespace lsxd
 
 #define HIPCHK(expr)                                                                                    \
@@ -130,24 +131,18 @@ struct lsx_ctx : lsxd::LsxPlan {        // the plan (lsx_plan.h: dimensions, tab
     uint8_t* d_prof_kind = nullptr;      // per column: 0 profiles handed over as arrays (or none yet), 1 built without, 2 with a velocity
     std::vector<uint8_t> prof_kind;      // host copy of the same
     bool atm_arrays = false;             // lsx_set_atmosphere has run: LSX_VBROAD / LSX_ADAMP can be read back
-    // column-independent tables of lsx_hip_emergent_rays, made on first use (lsx_rays.hip)
-    int32_t *d_rays_ptr = nullptr, *d_rays_tile = nullptr;
-    char* d_rays_ent = nullptr;
-    // ... and of lsx_hip_radiative_rates (lsx_rates.hip), with the pass's work arrays (allocated at first use, under rates_work_cap bytes)
-    int32_t *d_rates_ptr = nullptr, *d_rates_tile = nullptr, *d_rates_row = nullptr;
-    char* d_rates_ent = nullptr;
+    // column-independent tables of the final passes over the context's own grid, made on first use (final_tables, lsx_final_host.h)
+    int32_t *d_final_ptr = nullptr, *d_final_tile = nullptr, *d_final_row = nullptr;
+    lsxd::FinalEnt* d_final_ent = nullptr;
+    // the work arrays of lsx_hip_radiative_rates (lsx_rates.hip), allocated at first use, under rates_work_cap bytes
     double* d_rates_work = nullptr;
     size_t rates_work_doubles = 0, rates_work_cap = 0;      // cap 0: the default of include/lsx_hip_rates.h
-    // ... and of lsx_hip_radiative_losses (lsx_losses.hip): its own tables, the weights of a call (losses_wnu: the trapezoid rule in
-    // frequency over the merged grid, the default) and the pass's work arrays (allocated at first use, under losses_work_cap bytes)
-    int32_t *d_losses_ptr = nullptr, *d_losses_tile = nullptr, *d_losses_row = nullptr;
-    char* d_losses_ent = nullptr;
+    // ... of lsx_hip_radiative_losses (lsx_losses.hip), with the weights of a call (losses_wnu: the trapezoid rule in frequency over
+    // the merged grid, the default)
     double *d_losses_work = nullptr, *d_losses_wnu = nullptr;
     std::vector<double> losses_wnu;
     size_t losses_work_doubles = 0, losses_work_cap = 0;    // cap 0: the default of include/lsx_hip_losses.h
-    // ... and of lsx_hip_depth_rays (lsx_depth.hip), with the arrays of a pass (allocated at first use, under depth_work_cap bytes)
-    int32_t *d_depth_ptr = nullptr, *d_depth_tile = nullptr;
-    char* d_depth_ent = nullptr;
+    // ... of lsx_hip_depth_rays (lsx_depth.hip)
     double* d_depth_work = nullptr;
     size_t depth_work_doubles = 0, depth_work_cap = 0;      // cap 0: the default of include/lsx_hip_depth.h
     // ... and of lsx_hip_spectrum (lsx_spectrum.hip): the tables of a call (they depend on the call's wavelengths: rebuilt per call,

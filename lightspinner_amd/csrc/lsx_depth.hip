@@ -2,11 +2,11 @@
 // depth along up-going rays at arbitrary viewing angles, from what a context holds (include/lsx_hip_depth.h, lsx_hip_depth_rays).
 // Read-only on the context; gfx950 only.
 //
-// Reference lines restated here:
+// Reference lines restated here (the rest: lsx_final_dev.h, whose column set-up, start value and recurrence steps the walks use):
 //   rh_method.py:599-632           opacity, emissivity, source function of the up-going ray
 //   rh_method.py:231-239           line profile of the up-going ray at the new angle (ray-dependent profiles)
 //   formal_solver.py:129           dtau of an interval (summed from the top: tau)
-//   formal_solver.py:46-142, 203-207   the recurrence with its end-point quirk, thermalised lower boundary; I at EVERY depth
+//   formal_solver.py:117           I[kStart] = Istart: I at EVERY depth
 //
 // Mapping (that of k_emergent_rays, lsx_rays.hip): one wavefront = 64 consecutive wavelengths of the call's window of one column, a
 // lane owns one wavelength and carries a compile-time chunk of NM angles in registers.  Two walks per lane:
@@ -21,36 +21,16 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cmath>
-#include <vector>
 
 #include "../../include/lsx_hip.h"
-#include "lsx_ctx.h"
+#include "lsx_final_host.h"
 #include "lsx_voigt.h"
 
 using namespace lsxd;
 
 namespace {
 
-constexpr double kCLight = 2.99792458E+08;
-constexpr double kHPlanck = 6.6260755E-34;
-constexpr double kKBoltzmann = 1.380658E-23;
-constexpr double kNM_TO_M = 1.0E-09;
-constexpr double kHC = kHPlanck * kCLight;
 constexpr size_t kWorkCapDefault = (size_t)256 << 20;      // bytes (include/lsx_hip_depth.h)
-
-// one transition as one wavelength sees it; the entries of a wavelength are in table order (depth_tables)
-struct DepthEnt {
-    int32_t is_line;
-    int32_t li, lj;             // rows of n
-    int32_t row;                // lines: row of aDamp; continua: row of nsr
-    int32_t atom;               // lines: row of vBroad
-    int32_t phi_base, phi_len, phi_l;   // lines: the (tile, line) block of the profile store and the wavelength's place in it
-    double a;                   // lines: (hc/4pi) Bij; continua: alpha at this wavelength
-    double g;                   // lines: Bji / Bij
-    double Uc;                  // lines: (Aji / Bji) g (hc/4pi) Bij
-    double lambda0;             // lines: rest wavelength [nm]
-};
 
 struct DepthParams {
     int32_t Ns, Nspect, NLtot, Natoms, NlinesA, Ncont, L, Nrays;
@@ -60,7 +40,7 @@ struct DepthParams {
     int64_t til_col, phi_col, sca_col;
     const double *wavelength, *u_la, *exp2_tab, *voigt_W, *mu;
     const int32_t* la_ptr;      // [Nspect + 1] into ents
-    const DepthEnt* ents;
+    const FinalEnt* ents;
     const int32_t* la_tile;     // [Nspect][2]: tile, place in the tile
     const double *height, *temperature, *n, *nsr, *bgchi_T, *bgeta_T, *J_T, *E_T, *sca, *phi_T;
     const double *aDamp, *vBroad, *vlos;
@@ -69,15 +49,6 @@ struct DepthParams {
     const int32_t* bnd;         // the radiation boundary (lsx_dev.h, the boundary store), or null
     double* ztau1;              // [launch column][nmu][nla]
 };
-
-// utils.py:17-22 (as lsx_sweep.hip has it)
-__device__ __forceinline__ double planck(double temp, double wav)
-{
-    const double hc_Tkla = kHC / (kKBoltzmann * kNM_TO_M * wav) / temp;
-    const double x = kNM_TO_M * wav;
-    const double twohnu3_c2 = (2.0 * kHC) / (x * x * x);
-    return twohnu3_c2 / (exp(hc_Tkla) - 1.0);
-}
 
 template <int NM, bool PAR>
 __global__ void __launch_bounds__(64) k_depth_rays(const DepthParams p)
@@ -97,22 +68,8 @@ __global__ void __launch_bounds__(64) k_depth_rays(const DepthParams p)
     const size_t col = (size_t)p.col0 + blockIdx.y;
     // the lower boundary (include/lsx_hip_boundary.h): thermalised unless the column has been given ZERO (GIVEN is refused on the host)
     const bool lower_zero = p.bnd != nullptr && boundary_kind(p.bnd, col, LSX_BND_LOWER) == 0;
-    const int tile = p.la_tile[2 * la], j = p.la_tile[2 * la + 1];
-    const size_t toff = (size_t)tile * Ns * L + j;         // + k L: this wavelength in a tile-major stream
-    const double* __restrict__ bgchi = p.bgchi_T + col * p.til_col + toff;
-    const double* __restrict__ bgeta = p.bgeta_T + col * p.til_col + toff;
-    const double* __restrict__ Jd = p.J_T + col * p.til_col + toff;
-    const double* __restrict__ Eb = p.E_T ? p.E_T + col * p.til_col + toff : nullptr;
-    const double* __restrict__ sca = p.sca_per_lambda ? p.sca + col * p.sca_col + toff : p.sca + col * p.sca_col;
-    const int sstr = p.sca_per_lambda ? L : 1;
-    const double* __restrict__ z = p.height + col * Ns;
-    const double* __restrict__ n_col = p.n + col * (size_t)p.NLtot * Ns;
-    const double* __restrict__ nsr_col = p.nsr ? p.nsr + col * (size_t)p.Ncont * Ns : nullptr;
-    const int e0 = p.la_ptr[la], e1 = p.la_ptr[la + 1];
-    const bool raydep = !p.phi_compact && p.prof_kind && p.prof_kind[col] == 2;
-    const double* __restrict__ aD = raydep ? p.aDamp + col * (size_t)p.NlinesA * Ns : nullptr;
-    const double* __restrict__ vB = raydep ? p.vBroad + col * (size_t)p.Natoms * Ns : nullptr;
-    const double* __restrict__ vL = raydep ? p.vlos + col * Ns : nullptr;
+    const FinalColumn f = final_column(p, col, la);
+    const FinalAngles fa = final_angles(p, col);
     const double wav = p.wavelength[la], u_la = p.u_la[la];
     // this lane's cells: + (m Ns + k) nla
     const size_t plane = (size_t)Ns * p.nla;
@@ -137,27 +94,27 @@ __global__ void __launch_bounds__(64) k_depth_rays(const DepthParams p)
         for (int m = 0; m < NM; ++m) { tau[m] = 0.0; c_prev[m] = 0.0; zt1[m] = __builtin_nan(""); }
         double zprev = 0.0;
         // the stream operands of a depth are fetched a depth ahead: their loads are in flight before the depth's stores are issued
-        double f_c0 = bgchi[0], f_h0 = bgeta[0], f_sc = sca[0], f_J = Jd[0], f_E = Eb ? Eb[0] : 0.0;
+        double f_c0 = f.bgchi[0], f_h0 = f.bgeta[0], f_sc = f.sca[0], f_J = f.Jd[0], f_E = f.Eb ? f.Eb[0] : 0.0;
         for (int k = 0; k < Ns; ++k) {
-            const double zk = z[k];
+            const double zk = f.z[k];
             const double Ev = f_E;
             const double c0 = f_c0, h0 = f_h0 + f_sc * f_J;
             if (k + 1 < Ns) {
                 const size_t kn = (size_t)(k + 1);
-                f_c0 = bgchi[kn * L]; f_h0 = bgeta[kn * L]; f_sc = sca[kn * sstr]; f_J = Jd[kn * L];
-                f_E = Eb ? Eb[kn * L] : 0.0;
+                f_c0 = f.bgchi[kn * L]; f_h0 = f.bgeta[kn * L]; f_sc = f.sca[kn * f.sstr]; f_J = f.Jd[kn * L];
+                f_E = f.Eb ? f.Eb[kn * L] : 0.0;
             }
             // ---- opacity and emissivity at this depth (rh_method.py:599-632) ----
             double chi[NM], eta[NM];
 #pragma unroll
             for (int m = 0; m < NM; ++m) { chi[m] = c0; eta[m] = h0; }
-            for (int e = e0; e < e1; ++e) {
-                const DepthEnt& t = p.ents[e];
-                const double ni = n_col[(size_t)t.li * Ns + k], nj = n_col[(size_t)t.lj * Ns + k];
+            for (int e = f.e0; e < f.e1; ++e) {
+                const FinalEnt& t = p.ents[e];
+                const double ni = f.n_col[(size_t)t.li * Ns + k], nj = f.n_col[(size_t)t.lj * Ns + k];
                 if (t.is_line) {
                     const double nd = t.a * (ni - t.g * nj);          // n_i Vij - n_j Vji = nd phi, :279-280, :613
-                    if (raydep) {
-                        const double vb = vB[(size_t)t.atom * Ns + k], ad = aD[(size_t)t.row * Ns + k], vl = vL[k];
+                    if (fa.raydep) {
+                        const double vb = fa.vB[(size_t)t.atom * Ns + k], ad = fa.aD[(size_t)t.row * Ns + k], vl = fa.vL[k];
                         const double v = (wav - t.lambda0) * kCLight / (vb * t.lambda0);          // :234
                         const double nrm = sqrt(M_PI) * vb;
 #pragma unroll
@@ -175,7 +132,7 @@ __global__ void __launch_bounds__(64) k_depth_rays(const DepthParams p)
                         for (int m = 0; m < NM; ++m) { chi[m] += c1; eta[m] += h1; }
                     }
                 } else {
-                    const double pv = (nsr_col[(size_t)t.row * Ns + k] * Ev) * t.a;     // Vji = g_ij alpha, :284-285, :453-454
+                    const double pv = (f.nsr_col[(size_t)t.row * Ns + k] * Ev) * t.a;     // Vji = g_ij alpha, :284-285, :453-454
                     const double c1 = ni * t.a - nj * pv, h1 = nj * (u_la * pv);        // :286, :613-614
 #pragma unroll
                     for (int m = 0; m < NM; ++m) { chi[m] += c1; eta[m] += h1; }
@@ -213,18 +170,13 @@ __global__ void __launch_bounds__(64) k_depth_rays(const DepthParams p)
     }
 
     // ================= up: the recurrence on the lane's own chi and S; I at every depth =================
-    // state per angle (lsx_sweep.hip, generic path): linear rule chi_prev, S_prev, dtau_prev; parabolic rule the window (upwind,
-    // local, downwind) of the depth being finished
     double Iu[NM], c_k[NM], S_k[NM], c_u[NM], S_u[NM], dtau_prev[NM];
-#pragma unroll
-    for (int m = 0; m < NM; ++m) { Iu[m] = 0.0; c_k[m] = 1.0; S_k[m] = 0.0; c_u[m] = 1.0; S_u[m] = 0.0; dtau_prev[m] = 1.0; }
+    final_state_init(Iu, c_k, S_k, c_u, S_u, dtau_prev);
     double zk1 = 0.0, zk2 = 0.0;       // heights of the two depths below the current one
-    double B0 = 0.0, B1 = 0.0;
-    if (Ns >= 2) { B0 = planck(p.temperature[col * Ns + Ns - 2], wav); B1 = planck(p.temperature[col * Ns + Ns - 1], wav); }
 
     for (int k = Ns - 1; k >= 0; --k) {
         const int s = Ns - 1 - k;      // step along the up-going ray
-        const double zk = z[k];
+        const double zk = f.z[k];
         double chi[NM], Sd[NM];
 #pragma unroll
         for (int m = 0; m < NM; ++m) {
@@ -232,70 +184,37 @@ __global__ void __launch_bounds__(64) k_depth_rays(const DepthParams p)
             chi[m] = valid ? o_chi[o] : 1.0;       // (a spare lane keeps a harmless state of its own)
             Sd[m] = valid ? o_S[o] : 0.0;
         }
+        // the start value belongs to the depth below (Iu is still 0 there): I[kStart] = Istart, :117
+        if (s == 1 && !lower_zero)
+            thermal_start(planck(p.temperature[col * Ns + Ns - 1], wav), planck(p.temperature[col * Ns + Ns - 2], wav), fabs(zk1 - zk), zmu,
+                          c_k, chi, Iu);
         if constexpr (!PAR) {
-            // formal_solver.py:107-139 operation by operation, in the reference's order and without contraction into fused
-            // multiply-adds: two divisions per step where the sweeps share one reciprocal.  I is handed out at EVERY depth, and some
-            // of those values are heavy cancellations (the end point adds w1 dS of ITS interval to the previous interval's w0 S,
-            // :138-139: 2e5-fold on a three-depth column of the tests); there a reciprocal's 4e-15 would show as 1e-9, while the
-            // reference's own operations on the same chi and S give the reference's bits wherever no exponential is involved
-#pragma clang fp contract(off)
-            const double adz = fabs(zk1 - zk);
+            if (s == 1 && valid) {
 #pragma unroll
-            for (int m = 0; m < NM; ++m) {
-                if (s == 0) {
-                    S_k[m] = Sd[m];
-                    c_k[m] = chi[m];
-                    continue;
-                }
-                if (s == 1) {                                      // thermalised lower boundary, formal_solver.py:203-207
-                    const double dtau_uw = zmu[m] * (c_k[m] + chi[m]) * 0.5 * adz;
-                    Iu[m] = lower_zero ? 0.0 : B1 - (B0 - B1) / dtau_uw;
-                    if (valid) o_I[((size_t)m * Ns + k + 1) * p.nla] = Iu[m];        // I[kStart] = Istart, :117
-                }
-                const double dtau = 0.5 * (c_k[m] + chi[m]) * zmu[m] * adz;         // :107, :129
-                const double S = Sd[m];
-                const double dS = (S_k[m] - S) / dtau;                              // :111, :130
-                // formal_solver.py:138-139: the end point re-uses the previous interval's w and S[kEnd - dk] with the fresh dS
-                const bool last = k == 0;
-                double w0, w1;
-                w2(last ? dtau_prev[m] : dtau, w0, w1, etab);
-                const double Sx = last ? S_k[m] : S;
-                Iu[m] = Iu[m] * (1.0 - w0) + w0 * Sx + w1 * dS;                     // :126
-                dtau_prev[m] = dtau;
-                c_k[m] = chi[m];
-                S_k[m] = S;
-                if (valid) o_I[((size_t)m * Ns + k) * p.nla] = Iu[m];
+                for (int m = 0; m < NM; ++m) o_I[((size_t)m * Ns + k + 1) * p.nla] = Iu[m];
+            }
+            linear_step_ref(s, k == 0, fabs(zk1 - zk), zmu, chi, Sd, Iu, c_k, S_k, dtau_prev, etab);
+            if (s >= 1 && valid) {
+#pragma unroll
+                for (int m = 0; m < NM; ++m) o_I[((size_t)m * Ns + k) * p.nla] = Iu[m];
             }
         } else {
-            // monotonic parabolic rule (include/lsx.h, N4) as the sweep's generic instance: a depth is finished when its downwind
-            // neighbour is known.  Window after the shift: u = k + 2, k = k + 1, d = this depth
+            // a depth is finished when its downwind neighbour is known: from step 2 on Iu belongs to the depth below
 #pragma unroll
-            for (int m = 0; m < NM; ++m) {
-                const double c_d = chi[m], S_d = Sd[m];
-                if (s == 1) {
-                    const double dtau_uw = zmu[m] * (c_k[m] + c_d) * 0.5 * fabs(zk1 - zk);
-                    Iu[m] = lower_zero ? 0.0 : B1 - (B0 - B1) / dtau_uw;
-                    if (valid) o_I[((size_t)m * Ns + k + 1) * p.nla] = Iu[m];
-                }
-                if (s >= 2) {
-                    const double dtau_u = (c_u[m] + c_k[m]) * (0.5 * fabs(zk2 - zk1)) * zmu[m];
-                    const double dtau_d = (c_k[m] + c_d) * (0.5 * fabs(zk1 - zk)) * zmu[m];
-                    Iu[m] = parabolic_point(Iu[m], S_u[m], S_k[m], S_d, dtau_u, dtau_d, true, etab).I;
-                    if (valid) o_I[((size_t)m * Ns + k + 1) * p.nla] = Iu[m];
-                }
-                c_u[m] = c_k[m]; S_u[m] = S_k[m];
-                c_k[m] = c_d; S_k[m] = S_d;
+            for (int m = 0; m < NM; ++m) parabolic_step(s, zk, zk1, zk2, zmu[m], chi[m], Sd[m], Iu[m], c_k[m], S_k[m], c_u[m], S_u[m], etab);
+            if (s >= 1 && valid) {
+#pragma unroll
+                for (int m = 0; m < NM; ++m) o_I[((size_t)m * Ns + k + 1) * p.nla] = Iu[m];
             }
         }
         zk2 = zk1;
         zk1 = zk;
     }
-    if constexpr (PAR) {            // the end point: no downwind neighbour (the linear rule with its own interval's weights)
+    if constexpr (PAR) {
+        parabolic_end(zk1, zk2, zmu, Iu, c_k, S_k, c_u, S_u, etab);
+        if (valid) {
 #pragma unroll
-        for (int m = 0; m < NM; ++m) {
-            const double dtau_u = (c_u[m] + c_k[m]) * (0.5 * fabs(zk2 - zk1)) * zmu[m];
-            Iu[m] = parabolic_point(Iu[m], S_u[m], S_k[m], 0.0, dtau_u, 1.0, false, etab).I;
-            if (valid) o_I[(size_t)m * Ns * p.nla] = Iu[m];
+            for (int m = 0; m < NM; ++m) o_I[(size_t)m * Ns * p.nla] = Iu[m];
         }
     }
 }
@@ -305,55 +224,6 @@ void launch_chunk(const DepthParams& p, bool par, dim3 grid, hipStream_t st)
 {
     if (par) hipLaunchKernelGGL((k_depth_rays<NM, true>), grid, dim3(64), 0, st, p);
     else hipLaunchKernelGGL((k_depth_rays<NM, false>), grid, dim3(64), 0, st, p);
-}
-
-// column-independent tables of the entry, made on first use: per wavelength its active transitions in table order and its
-// place in the tile-major streams
-int depth_tables(lsx_ctx* c)
-{
-    if (c->d_depth_ptr) return LSX_OK;
-    const int Nspect = c->Nspect;
-    std::vector<int32_t> la_tile(2 * (size_t)Nspect, 0), ptr(Nspect + 1, 0);
-    std::vector<int> tile_of(Nspect, -1);
-    for (size_t t = 0; t < c->tiles.size(); ++t)
-        for (int q = 0; q < c->tiles[t].nla; ++q) {
-            const int la = c->tiles[t].la0 + q;
-            tile_of[la] = (int)t;
-            la_tile[2 * la] = (int32_t)t;
-            la_tile[2 * la + 1] = q;
-        }
-    std::vector<DepthEnt> ents;
-    for (int la = 0; la < Nspect; ++la) {
-        if (tile_of[la] < 0) return fail(LSX_EDEVICE, "lsx_hip_depth_rays: wavelength %d belongs to no tile", la);
-        const DevTile& tl = c->tiles[tile_of[la]];
-        for (int t = 0; t < c->Ntrans; ++t) {
-            if (!c->active[(size_t)t * Nspect + la]) continue;
-            const DevTrans& h = c->htrans[t];
-            DepthEnt e{};
-            e.is_line = h.is_line; e.li = h.li; e.lj = h.lj; e.row = c->trans_row[t]; e.atom = h.atom;
-            if (h.is_line) {
-                const DevSlot* sl = nullptr;
-                for (int u = 0; u < tl.nL; ++u)
-                    if (c->slots[tl.slot0 + u].trans == t) sl = &c->slots[tl.slot0 + u];
-                if (!sl || !(sl->flags & SLOT_LINE) || la < sl->first || la >= sl->first + sl->len)
-                    return fail(LSX_EDEVICE, "lsx_hip_depth_rays: line %d has no profile block at wavelength %d", t, la);
-                e.phi_base = sl->base; e.phi_len = sl->len; e.phi_l = la - sl->first;
-                e.a = h.cB; e.g = h.gij; e.Uc = h.AB * (h.gij * h.cB); e.lambda0 = h.lambda0;
-            } else {
-                e.a = c->alpha[h.wl_off + (la - h.Nblue)];
-            }
-            ents.push_back(e);
-        }
-        ptr[la + 1] = (int32_t)ents.size();
-    }
-    if (ents.empty()) ents.push_back(DepthEnt{});
-    std::vector<char> bytes((const char*)ents.data(), (const char*)ents.data() + ents.size() * sizeof(DepthEnt));
-    int rc = upload(&c->d_depth_tile, la_tile, c->stream);
-    if (!rc) rc = upload(&c->d_depth_ent, bytes, c->stream);
-    if (!rc) rc = upload(&c->d_depth_ptr, ptr, c->stream);       // (last: its presence marks the set complete)
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(c->stream));                      // the host vectors go out of scope
-    return LSX_OK;
 }
 
 } // namespace
@@ -377,11 +247,9 @@ extern "C" int lsx_hip_depth_rays(lsx_ctx* c, int32_t nmu, const double* mu, int
     // ---- everything is checked on the host before anything is launched ----
     if (!c || !mu) return fail(LSX_EINVAL, "lsx_hip_depth_rays: null argument");
     if (!chi && !S && !tau && !I && !contrib && !z_tau1) return fail(LSX_EINVAL, "lsx_hip_depth_rays: all six outputs are NULL");
-    if (nmu < 1) return fail(LSX_EINVAL, "lsx_hip_depth_rays: nmu = %d, need at least one angle", (int)nmu);
-    for (int m = 0; m < nmu; ++m)
-        if (!(mu[m] > 0.0 && mu[m] <= 1.0)) return fail(LSX_EINVAL, "lsx_hip_depth_rays: mu[%d] = %g is outside (0, 1]", m, mu[m]);
-    if (col0 < 0 || ncol < 1 || (int64_t)col0 + ncol > c->ncol)
-        return fail(LSX_EINVAL, "lsx_hip_depth_rays: columns [%d, %d) are outside the context's %d", (int)col0, (int)col0 + (int)ncol, c->ncol);
+    int rc = final_check_angles("lsx_hip_depth_rays", nmu, mu);
+    if (!rc) rc = final_check_range(c, "lsx_hip_depth_rays", col0, ncol);
+    if (rc) return rc;
     if (nla < 1) return fail(LSX_EINVAL, "lsx_hip_depth_rays: nla = %d, need at least one wavelength", (int)nla);
     if (la0 < 0 || (int64_t)la0 + nla > c->Nspect)
         return fail(LSX_EINVAL, "lsx_hip_depth_rays: wavelengths [%d, %d) are outside the grid's %d", (int)la0, (int)la0 + (int)nla, c->Nspect);
@@ -390,22 +258,10 @@ extern "C" int lsx_hip_depth_rays(lsx_ctx* c, int32_t nmu, const double* mu, int
     if ((chi || S || tau || I || contrib) && nbytes_each != (size_t)ncol * per * 8)
         return fail(LSX_EINVAL, "lsx_hip_depth_rays: nbytes_each does not match [ncol][nmu][Nspace][nla]");
     if (z_tau1 && nbytes_z != (size_t)ncol * zper * 8) return fail(LSX_EINVAL, "lsx_hip_depth_rays: nbytes_z does not match [ncol][nmu][nla]");
-    if (c->Nspace < 3) return fail(LSX_EUNSUPPORTED, "lsx_hip_depth_rays: needs Nspace >= 3");
-    for (int q = col0; q < col0 + ncol; ++q) {
-        if (!c->bnd_kind.empty() && c->bnd_kind[2 * (size_t)q] == LSX_BOUNDARY_GIVEN)
-            return fail(LSX_EUNSUPPORTED, "lsx_hip_depth_rays: column %d has a GIVEN lower boundary (lsx_hip_set_boundary): its intensity was handed "
-                                          "over on the context's own rays and wavelengths and is not known at another angle", q);
-        if (!c->phi_set[q])
-            return fail(LSX_EINVAL, "lsx_hip_depth_rays: column %d has no line profiles (lsx_set_columns with phi == NULL must be "
-                                    "followed by lsx_set_line_profiles)", q);
-        if (c->Nlines && !c->phi_compact && (c->prof_kind.empty() || !c->prof_kind[q]))
-            return fail(LSX_EUNSUPPORTED, "lsx_hip_depth_rays: the ray-dependent line profiles of column %d were handed over as arrays "
-                                          "(lsx_set_columns): the library cannot know them at another angle.  Build them with "
-                                          "lsx_set_line_profiles or lsx_set_atmosphere", q);
-    }
+    if ((rc = final_check_depths(c, "lsx_hip_depth_rays"))) return rc;
+    if ((rc = final_check_columns(c, "lsx_hip_depth_rays", col0, ncol, FINAL_OTHER_ANGLE))) return rc;
     HIPCHK(hipSetDevice(c->device));
-    int rc = depth_tables(c);
-    if (rc) return rc;
+    if ((rc = final_tables(c, "lsx_hip_depth_rays"))) return rc;
 
     // columns per pass: the arrays of a pass stay under the cap (one column's need if that alone is more)
     const size_t wcol = 5 * per + zper;
@@ -430,7 +286,7 @@ extern "C" int lsx_hip_depth_rays(lsx_ctx* c, int32_t nmu, const double* mu, int
     p.phi_compact = c->phi_compact; p.sca_per_lambda = c->sca_per_lambda; p.phi_G = c->phi_group;
     p.til_col = (int64_t)c->til_col; p.phi_col = (int64_t)c->phi_col; p.sca_col = (int64_t)c->sca_col;
     p.wavelength = c->d_wavelength; p.u_la = c->d_u_la; p.exp2_tab = c->d_exp2_tab; p.voigt_W = c->d_voigt_w; p.mu = d_mu;
-    p.la_ptr = c->d_depth_ptr; p.ents = reinterpret_cast<const DepthEnt*>(c->d_depth_ent); p.la_tile = c->d_depth_tile;
+    p.la_ptr = c->d_final_ptr; p.ents = c->d_final_ent; p.la_tile = c->d_final_tile;
     p.height = c->d_height; p.temperature = c->d_temperature; p.n = c->d_n; p.nsr = c->d_nsr;
     p.bnd = c->d_bnd;
     p.bgchi_T = c->d_bgchi; p.bgeta_T = c->d_bgeta; p.J_T = c->d_J[c->jcur];      // what lsx_get(LSX_J) returns at this moment

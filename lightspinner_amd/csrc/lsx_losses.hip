@@ -1,12 +1,11 @@
 // lsx_losses.hip -- final-pass formal solution: the radiative flux, its divergence (the net radiative cooling) and how that cooling
 // divides among the transitions, from what a context holds (include/lsx_hip_losses.h, lsx_hip_radiative_losses).  Read-only on the
-// context; gfx950 only.  A file of its own beside lsx_rates.hip, whose walk it restates: nothing of the other passes is edited.
+// context; gfx950 only.  A file of its own beside lsx_rates.hip, with the same walk.
 //
-// Reference lines restated here:
+// Reference lines restated here (the rest: lsx_final_dev.h, whose column set-up, start values and recurrence steps the walk uses):
 //   rh_method.py:599-632           opacity, emissivity, source function
 //   rh_method.py:661-665           wlamu = wla (wmu / 2) 4 pi
 //   rh_method.py:425-455, 157-196  wla of a line (wlambda wphi / hc) and of a continuum (wlambda / lambda / h), g_ij
-//   formal_solver.py:46-142, 203-209   the recurrence with its end-point quirk; boundary values 0 (top), thermalised (bottom)
 //
 // Two stages, no atomics, every sum in a fixed order:
 //   k_losses_pass<NM, PAR>  the mapping of k_rates_pass: one wavefront = 64 consecutive wavelengths of one column, a lane owns one
@@ -25,33 +24,15 @@
 
 #include <algorithm>
 #include <cmath>
-#include <vector>
 
 #include "../../include/lsx_hip.h"
-#include "lsx_ctx.h"
+#include "lsx_final_host.h"
 
 using namespace lsxd;
 
 namespace {
 
-constexpr double kCLight = 2.99792458E+08;
-constexpr double kHPlanck = 6.6260755E-34;
-constexpr double kKBoltzmann = 1.380658E-23;
-constexpr double kNM_TO_M = 1.0E-09;
-constexpr double kHC = kHPlanck * kCLight;
 constexpr size_t kWorkCapDefault = (size_t)256 << 20;      // bytes (include/lsx_hip_losses.h)
-
-// one transition as one wavelength sees it; the entries of a wavelength are in table order
-struct LossEnt {
-    int32_t is_line;
-    int32_t li, lj;             // rows of n
-    int32_t row;                // continua: row of nsr
-    int32_t phi_base, phi_len, phi_l;   // lines: the (tile, line) block of the profile store and the wavelength's place in it
-    int32_t cell;               // lines: the wavelength's place in the line pool of the work array (DevTrans.phi_off + lt)
-    double a;                   // lines: (hc/4pi) Bij; continua: alpha at this wavelength
-    double g;                   // lines: Bji / Bij
-    double Uc;                  // lines: (Aji / Bji) g (hc/4pi) Bij
-};
 
 struct LossParams {
     int32_t Ns, Nspect, NLtot, Ncont, L, Nrays, SNl, Ntrans;
@@ -61,7 +42,7 @@ struct LossParams {
     int64_t til_col, phi_col, sca_col;
     const double *wavelength, *u_la, *exp2_tab, *zmu, *muz, *wmuh, *wl, *alpha, *wnu;
     const int32_t* la_ptr;      // [Nspect + 1] into ents
-    const LossEnt* ents;
+    const FinalEnt* ents;
     const int32_t* la_tile;     // [Nspect][2]: tile, place in the tile
     const DevTrans* trans;
     const int32_t* trans_row;   // per transition: continua: row of nsr
@@ -73,15 +54,6 @@ struct LossParams {
     const int32_t* bnd;         // the radiation boundary (lsx_dev.h, the boundary store): null = thermalised below, zero above, as it was
     double *F, *Q, *Qt, *Ht, *Dt;   // device results of a pass: [launch column][k], [launch column][Ntrans][k], [launch column][Nspect][k]
 };
-
-// utils.py:17-22 (as lsx_sweep.hip has it)
-__device__ __forceinline__ double planck(double temp, double wav)
-{
-    const double hc_Tkla = kHC / (kKBoltzmann * kNM_TO_M * wav) / temp;
-    const double x = kNM_TO_M * wav;
-    const double twohnu3_c2 = (2.0 * kHC) / (x * x * x);
-    return twohnu3_c2 / (exp(hc_Tkla) - 1.0);
-}
 
 // waves per SIMD of the pass's instances by rays per lane, as DESIGN.md 4.19 states them: asked of the compiler, so that the boundary's
 // arm of the start values moves no instance to another count.  What holds this table, the one in DESIGN.md and the
@@ -104,18 +76,7 @@ k_losses_pass(const LossParams p)
     const bool valid = la_raw < p.Nspect;
     const int la = valid ? la_raw : p.Nspect - 1;          // every lane walks a wavelength (w2 / w3 are wave-wide); spare ones store nothing
     const size_t col = (size_t)p.col0 + blockIdx.y;
-    const int tile = p.la_tile[2 * la], j = p.la_tile[2 * la + 1];
-    const size_t toff = (size_t)tile * Ns * L + j;         // + k L: this wavelength in a tile-major stream
-    const double* __restrict__ bgchi = p.bgchi_T + col * p.til_col + toff;
-    const double* __restrict__ bgeta = p.bgeta_T + col * p.til_col + toff;
-    const double* __restrict__ Jd = p.J_T + col * p.til_col + toff;
-    const double* __restrict__ Eb = p.E_T ? p.E_T + col * p.til_col + toff : nullptr;
-    const double* __restrict__ sca = p.sca_per_lambda ? p.sca + col * p.sca_col + toff : p.sca + col * p.sca_col;
-    const int sstr = p.sca_per_lambda ? L : 1;
-    const double* __restrict__ z = p.height + col * Ns;
-    const double* __restrict__ n_col = p.n + col * (size_t)p.NLtot * Ns;
-    const double* __restrict__ nsr_col = p.nsr ? p.nsr + col * (size_t)p.Ncont * Ns : nullptr;
-    const int e0 = p.la_ptr[la], e1 = p.la_ptr[la + 1];
+    const FinalColumn f = final_column(p, col, la);
     const double wav = p.wavelength[la], u_la = p.u_la[la];
     const size_t wbase = (size_t)blockIdx.y * Ns * p.Nspect + la;          // + k Nspect: this wavelength's cell of H, D and Jp
     double2* PP = p.PP + (size_t)blockIdx.y * Ns * p.SNl;                  // + k SNl + cell
@@ -132,7 +93,7 @@ k_losses_pass(const LossParams p)
         const bool up = dir == 1;
         const bool fresh = p.first && !up;                 // the first visit of the call: the sums start here
         // the profile of line entry t at depth kd for ray m of this group
-        auto phi_at = [&](const LossEnt& t, int kd, int m) -> double {
+        auto phi_at = [&](const FinalEnt& t, int kd, int m) -> double {
             const size_t x = p.phi_compact ? (size_t)kd : ((size_t)dir * Ns + kd) * p.Nrays + (p.mu0 + m);
             return p.phi_T[phi_elem(col, p.phi_G, (size_t)p.phi_col, (size_t)t.phi_base, x, t.phi_len, t.phi_l)];
         };
@@ -150,8 +111,8 @@ k_losses_pass(const LossParams p)
             p.Jp[w] = (fresh ? 0.0 : p.Jp[w]) + js;
             p.Hw[w] = (fresh ? 0.0 : p.Hw[w]) + (up ? hs : -hs);
             p.Dw[w] = (fresh ? 0.0 : p.Dw[w]) + ds;
-            for (int e = e0; e < e1; ++e) {
-                const LossEnt& t = p.ents[e];
+            for (int e = f.e0; e < f.e1; ++e) {
+                const FinalEnt& t = p.ents[e];
                 if (!t.is_line) continue;
                 double ps = 0.0, fs = 0.0;
                 if (p.phi_compact) {
@@ -181,38 +142,35 @@ k_losses_pass(const LossParams p)
             accumulate(kd, Iv, cv, ev);
         };
 
-        // state of the recurrence per ray (lsx_sweep.hip, generic path): linear rule chi_prev, S_prev, dtau_prev; parabolic rule the
-        // window (upwind, local, downwind) of the depth being finished
         double Iu[NM], c_k[NM], S_k[NM], c_u[NM], S_u[NM], dtau_prev[NM];
-#pragma unroll
-        for (int m = 0; m < NM; ++m) { Iu[m] = 0.0; c_k[m] = 1.0; S_k[m] = 0.0; c_u[m] = 1.0; S_u[m] = 0.0; dtau_prev[m] = 1.0; }
+        final_state_init(Iu, c_k, S_k, c_u, S_u, dtau_prev);
         double zk1 = 0.0, zk2 = 0.0;       // heights of the two depths behind the current one
         int k1 = 0;                        // the depth behind the current one
 
         // the stream operands of a depth, fetched one depth ahead
         const int kfirst = up ? Ns - 1 : 0;
-        double n_c0 = bgchi[(size_t)kfirst * L], n_be = bgeta[(size_t)kfirst * L], n_sc = sca[(size_t)kfirst * sstr],
-               n_jd = Jd[(size_t)kfirst * L], n_ev = Eb ? Eb[(size_t)kfirst * L] : 0.0;
+        double n_c0 = f.bgchi[(size_t)kfirst * L], n_be = f.bgeta[(size_t)kfirst * L], n_sc = f.sca[(size_t)kfirst * f.sstr],
+               n_jd = f.Jd[(size_t)kfirst * L], n_ev = f.Eb ? f.Eb[(size_t)kfirst * L] : 0.0;
 
         for (int s = 0; s < Ns; ++s) {     // step along the ray
             const int k = up ? Ns - 1 - s : s;
-            const double zk = z[k];
+            const double zk = f.z[k];
             const double c0 = n_c0, h0 = n_be + n_sc * n_jd, Ev = n_ev;
             if (s + 1 < Ns) {              // the next depth's operands: in flight before this depth's stores
                 const int kn = up ? k - 1 : k + 1;
-                n_c0 = bgchi[(size_t)kn * L];
-                n_be = bgeta[(size_t)kn * L];
-                n_sc = sca[(size_t)kn * sstr];
-                n_jd = Jd[(size_t)kn * L];
-                n_ev = Eb ? Eb[(size_t)kn * L] : 0.0;
+                n_c0 = f.bgchi[(size_t)kn * L];
+                n_be = f.bgeta[(size_t)kn * L];
+                n_sc = f.sca[(size_t)kn * f.sstr];
+                n_jd = f.Jd[(size_t)kn * L];
+                n_ev = f.Eb ? f.Eb[(size_t)kn * L] : 0.0;
             }
             // ---- opacity and emissivity at this depth (rh_method.py:599-632) ----
             double chi[NM], eta[NM];
 #pragma unroll
             for (int m = 0; m < NM; ++m) { chi[m] = c0; eta[m] = h0; }
-            for (int e = e0; e < e1; ++e) {
-                const LossEnt& t = p.ents[e];
-                const double ni = n_col[(size_t)t.li * Ns + k], nj = n_col[(size_t)t.lj * Ns + k];
+            for (int e = f.e0; e < f.e1; ++e) {
+                const FinalEnt& t = p.ents[e];
+                const double ni = f.n_col[(size_t)t.li * Ns + k], nj = f.n_col[(size_t)t.lj * Ns + k];
                 if (t.is_line) {
                     const double nd = t.a * (ni - t.g * nj);          // n_i Vij - n_j Vji = nd phi, :279-280, :613
                     if (p.phi_compact) {
@@ -229,102 +187,32 @@ k_losses_pass(const LossParams p)
                         }
                     }
                 } else {
-                    const double pv = (nsr_col[(size_t)t.row * Ns + k] * Ev) * t.a;     // Vji = g_ij alpha, :284-285, :453-454
+                    const double pv = (f.nsr_col[(size_t)t.row * Ns + k] * Ev) * t.a;     // Vji = g_ij alpha, :284-285, :453-454
                     const double c1 = ni * t.a - nj * pv, h1 = nj * (u_la * pv);        // :286, :613-614
 #pragma unroll
                     for (int m = 0; m < NM; ++m) { chi[m] += c1; eta[m] += h1; }
                 }
             }
             // ---- the recurrence at this depth ----
-            double B0 = 0.0, B1 = 0.0;
-            if (up && s == 1) { B0 = planck(p.temperature[col * Ns + Ns - 2], wav); B1 = planck(p.temperature[col * Ns + Ns - 1], wav); }
-            if (s == 1 && p.bnd != nullptr) {
-                // a boundary has been set (include/lsx_hip_boundary.h): the kind of this direction's end of the column (wave-uniform:
-                // a block is one column); the thermalised value of the upper end is the mirror image of the lower one (k1: the end's
-                // depth, k: the next one)
-                const int end = up ? LSX_BND_LOWER : LSX_BND_UPPER;
-                const int kind = boundary_kind(p.bnd, col, end);
-                if (kind == 1) {
-                    const double Bn = planck(p.temperature[col * Ns + k], wav), Be = planck(p.temperature[col * Ns + k1], wav);
-#pragma unroll
-                    for (int m = 0; m < NM; ++m) {
-                        const double dtau_uw = zmu[m] * (c_k[m] + chi[m]) * 0.5 * fabs(zk1 - zk);
-                        Iu[m] = Be - (Bn - Be) / dtau_uw;
-                    }
-                } else if (kind == 2) {
-                    const double* given = boundary_given(p.bnd, end, col, (size_t)p.Nspect * p.Nrays) + (size_t)la * p.Nrays + p.mu0;
-#pragma unroll
-                    for (int m = 0; m < NM; ++m) Iu[m] = given[m];
-                } else {
-#pragma unroll
-                    for (int m = 0; m < NM; ++m) Iu[m] = 0.0;
-                }
-                accumulate_cs(k1, Iu, c_k, S_k);
-            } else if (s == 1) {           // the value the ray starts with belongs to the depth behind: 0 at the top, thermalised at the bottom
-#pragma unroll
-                for (int m = 0; m < NM; ++m) {
-                    if (up) {
-                        const double dtau_uw = zmu[m] * (c_k[m] + chi[m]) * 0.5 * fabs(zk1 - zk);
-                        Iu[m] = B1 - (B0 - B1) / dtau_uw;
-                    } else {
-                        Iu[m] = 0.0;
-                    }
-                }
+            if (s == 1) {                  // the value the rays start with belongs to the depth behind
+                final_start(p, col, la, up, k1, k, wav, fabs(zk1 - zk), zmu, c_k, chi, Iu);
                 accumulate_cs(k1, Iu, c_k, S_k);
             }
             if constexpr (!PAR) {
-                // formal_solver.py:107-139 as the sweep's generic path has it: the two divisions of a step share one reciprocal
-                const double hdz = 0.5 * fabs(zk1 - zk);
-#pragma unroll
-                for (int m = 0; m < NM; ++m) {
-                    if (s == 0) {
-                        const double rchi = rcp(chi[m]);
-                        S_k[m] = eta[m] * rchi;
-                        c_k[m] = chi[m];
-                        continue;
-                    }
-                    const double dtau = (c_k[m] + chi[m]) * (hdz * zmu[m]);
-                    const double rcd = rcp(chi[m] * dtau);
-                    const double rchi = rcd * dtau, rdt = rcd * chi[m];
-                    const double S = eta[m] * rchi;                    // :632
-                    const double dS = (S_k[m] - S) * rdt;
-                    // formal_solver.py:138-139: the end point re-uses the previous interval's w and S[kEnd - dk] with the fresh dS
-                    const bool last = s == Ns - 1;
-                    double w0, w1;
-                    w2(last ? dtau_prev[m] : dtau, w0, w1, etab);
-                    const double Sx = last ? S_k[m] : S;
-                    Iu[m] = Iu[m] * (1.0 - w0) + w0 * Sx + w1 * dS;
-                    dtau_prev[m] = dtau;
-                    c_k[m] = chi[m];
-                    S_k[m] = S;
-                }
+                linear_step(s, s == Ns - 1, 0.5 * fabs(zk1 - zk), zmu, chi, eta, Iu, c_k, S_k, dtau_prev, etab);
                 if (s >= 1) accumulate(k, Iu, chi, eta);
             } else {
-                // monotonic parabolic rule (include/lsx.h, N4) as the sweep's generic instance: a depth is finished when its downwind
-                // neighbour is known.  Window after the shift: u = two behind, k = one behind, d = this depth
 #pragma unroll
-                for (int m = 0; m < NM; ++m) {
-                    const double c_d = chi[m], S_d = eta[m] / chi[m];
-                    if (s >= 2) {
-                        const double dtau_u = (c_u[m] + c_k[m]) * (0.5 * fabs(zk2 - zk1)) * zmu[m];
-                        const double dtau_d = (c_k[m] + c_d) * (0.5 * fabs(zk1 - zk)) * zmu[m];
-                        Iu[m] = parabolic_point(Iu[m], S_u[m], S_k[m], S_d, dtau_u, dtau_d, true, etab).I;
-                    }
-                    c_u[m] = c_k[m]; S_u[m] = S_k[m];
-                    c_k[m] = c_d; S_k[m] = S_d;
-                }
+                for (int m = 0; m < NM; ++m)
+                    parabolic_step(s, zk, zk1, zk2, zmu[m], chi[m], eta[m] / chi[m], Iu[m], c_k[m], S_k[m], c_u[m], S_u[m], etab);
                 if (s >= 2) accumulate_cs(k1, Iu, c_u, S_u);      // (after the shift the finished depth is the window's u)
             }
             zk2 = zk1;
             zk1 = zk;
             k1 = k;
         }
-        if constexpr (PAR) {            // the end point: no downwind neighbour (the linear rule with its own interval's weights)
-#pragma unroll
-            for (int m = 0; m < NM; ++m) {
-                const double dtau_u = (c_u[m] + c_k[m]) * (0.5 * fabs(zk2 - zk1)) * zmu[m];
-                Iu[m] = parabolic_point(Iu[m], S_u[m], S_k[m], 0.0, dtau_u, 1.0, false, etab).I;
-            }
+        if constexpr (PAR) {
+            parabolic_end(zk1, zk2, zmu, Iu, c_k, S_k, c_u, S_u, etab);
             accumulate_cs(k1, Iu, c_k, S_k);
         }
     }
@@ -415,65 +303,6 @@ void launch_pass(const LossParams& p, bool par, dim3 grid, hipStream_t st)
     else hipLaunchKernelGGL((k_losses_pass<NM, false>), grid, dim3(64), 0, st, p);
 }
 
-// column-independent tables of the entry, made on first use: per wavelength its active transitions in table order and its
-// place in the tile-major streams (as lsx_rates.hip builds its own)
-int losses_tables(lsx_ctx* c)
-{
-    if (c->d_losses_ptr) return LSX_OK;
-    const int Nspect = c->Nspect;
-    std::vector<int32_t> la_tile(2 * (size_t)Nspect, 0), ptr(Nspect + 1, 0);
-    std::vector<int> tile_of(Nspect, -1);
-    for (size_t t = 0; t < c->tiles.size(); ++t)
-        for (int q = 0; q < c->tiles[t].nla; ++q) {
-            const int la = c->tiles[t].la0 + q;
-            tile_of[la] = (int)t;
-            la_tile[2 * la] = (int32_t)t;
-            la_tile[2 * la + 1] = q;
-        }
-    std::vector<LossEnt> ents;
-    for (int la = 0; la < Nspect; ++la) {
-        if (tile_of[la] < 0) return fail(LSX_EDEVICE, "lsx_hip_radiative_losses: wavelength %d belongs to no tile", la);
-        const DevTile& tl = c->tiles[tile_of[la]];
-        for (int t = 0; t < c->Ntrans; ++t) {
-            if (!c->active[(size_t)t * Nspect + la]) continue;
-            const DevTrans& h = c->htrans[t];
-            const int lt = la - h.Nblue;
-            if (lt < 0 || lt >= h.Nlam) return fail(LSX_EDEVICE, "lsx_hip_radiative_losses: transition %d is active outside its range at wavelength %d", t, la);
-            LossEnt e{};
-            e.is_line = h.is_line; e.li = h.li; e.lj = h.lj; e.row = c->trans_row[t];
-            if (h.is_line) {
-                const DevSlot* sl = nullptr;
-                for (int u = 0; u < tl.nL; ++u)
-                    if (c->slots[tl.slot0 + u].trans == t) sl = &c->slots[tl.slot0 + u];
-                if (!sl || !(sl->flags & SLOT_LINE) || la < sl->first || la >= sl->first + sl->len)
-                    return fail(LSX_EDEVICE, "lsx_hip_radiative_losses: line %d has no profile block at wavelength %d", t, la);
-                e.phi_base = sl->base; e.phi_len = sl->len; e.phi_l = la - sl->first;
-                e.cell = h.phi_off + lt;
-                e.a = h.cB; e.g = h.gij; e.Uc = h.AB * (h.gij * h.cB);
-            } else {
-                e.a = c->alpha[h.wl_off + lt];
-            }
-            ents.push_back(e);
-        }
-        ptr[la + 1] = (int32_t)ents.size();
-    }
-    if (ents.empty()) ents.push_back(LossEnt{});
-    std::vector<char> bytes((const char*)ents.data(), (const char*)ents.data() + ents.size() * sizeof(LossEnt));
-    std::vector<int32_t> rows(c->trans_row.begin(), c->trans_row.end());
-    rows.resize(std::max(1, c->Ntrans), 0);
-    // the trapezoid rule in frequency over the merged grid, formed once in the grid code (lsx_grid.cpp)
-    c->losses_wnu.assign((size_t)Nspect, 0.0);
-    int rc = lsx_hip_frequency_weights(Nspect, c->wave.data(), c->losses_wnu.data());
-    if (!rc) rc = dmalloc(&c->d_losses_wnu, (size_t)Nspect);
-    if (!rc) rc = upload(&c->d_losses_tile, la_tile, c->stream);
-    if (!rc) rc = upload(&c->d_losses_row, rows, c->stream);
-    if (!rc) rc = upload(&c->d_losses_ent, bytes, c->stream);
-    if (!rc) rc = upload(&c->d_losses_ptr, ptr, c->stream);      // (last: its presence marks the set complete)
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(c->stream));                      // the host vectors go out of scope
-    return LSX_OK;
-}
-
 // H, D, Jp and the (P, Phi) pairs of the lines
 size_t work_doubles_per_column(const lsx_ctx* c) { return (size_t)c->Nspace * (3 * (size_t)c->Nspect + 2 * (size_t)c->SNl); }
 
@@ -497,24 +326,25 @@ extern "C" int lsx_hip_radiative_losses(lsx_ctx* c, int32_t col0, int32_t ncol, 
     // ---- everything is checked on the host before anything is launched ----
     if (!c) return fail(LSX_EINVAL, "lsx_hip_radiative_losses: null context");
     if (!F && !Q && !Qt && !H && !D) return fail(LSX_EINVAL, "lsx_hip_radiative_losses: all five outputs are NULL");
-    if (c->Nspace < 3) return fail(LSX_EUNSUPPORTED, "lsx_hip_radiative_losses: needs Nspace >= 3");
-    if (col0 < 0 || ncol < 1 || (int64_t)col0 + ncol > c->ncol)
-        return fail(LSX_EINVAL, "lsx_hip_radiative_losses: columns [%d, %d) are outside the context's %d", (int)col0, (int)col0 + (int)ncol, c->ncol);
+    int rc = final_check_depths(c, "lsx_hip_radiative_losses");
+    if (!rc) rc = final_check_range(c, "lsx_hip_radiative_losses", col0, ncol);
+    if (rc) return rc;
     const size_t Ns = (size_t)c->Nspace, Nspect = (size_t)c->Nspect;
     const size_t per_t = (size_t)c->Ntrans * Ns, per_m = Nspect * Ns;
     if ((F || Q) && nbytes_FQ != (size_t)ncol * Ns * 8) return fail(LSX_EINVAL, "lsx_hip_radiative_losses: nbytes_FQ does not match [ncol][Nspace]");
     if (Qt && nbytes_Qt != (size_t)ncol * per_t * 8) return fail(LSX_EINVAL, "lsx_hip_radiative_losses: nbytes_Qt does not match [ncol][Ntrans][Nspace]");
     if ((H || D) && nbytes_HD != (size_t)ncol * per_m * 8) return fail(LSX_EINVAL, "lsx_hip_radiative_losses: nbytes_HD does not match [ncol][Nspect][Nspace]");
-    for (int q = col0; q < col0 + ncol; ++q)
-        if (!c->phi_set[q])
-            return fail(LSX_EINVAL, "lsx_hip_radiative_losses: column %d has no line profiles (lsx_set_columns with phi == NULL must be "
-                                    "followed by lsx_set_line_profiles)", q);
+    if ((rc = final_check_columns(c, "lsx_hip_radiative_losses", col0, ncol, FINAL_OWN_RAYS))) return rc;
     if (wnu)
         for (size_t la = 0; la < Nspect; ++la)
             if (!std::isfinite(wnu[la])) return fail(LSX_EINVAL, "lsx_hip_radiative_losses: wnu[%zu] is not finite", la);
     HIPCHK(hipSetDevice(c->device));
-    int rc = losses_tables(c);
-    if (rc) return rc;
+    if ((rc = final_tables(c, "lsx_hip_radiative_losses"))) return rc;
+    if (!c->d_losses_wnu) {        // the trapezoid rule in frequency over the merged grid, formed once in the grid code (lsx_grid.cpp)
+        c->losses_wnu.assign(Nspect, 0.0);
+        if ((rc = lsx_hip_frequency_weights(c->Nspect, c->wave.data(), c->losses_wnu.data()))) return rc;
+        if ((rc = dmalloc(&c->d_losses_wnu, Nspect))) return rc;
+    }
 
     // columns per pass: the work arrays stay under the cap (one column's need if that alone is more; a grid's y limit)
     const size_t wcol = work_doubles_per_column(c);
@@ -541,8 +371,8 @@ extern "C" int lsx_hip_radiative_losses(lsx_ctx* c, int32_t col0, int32_t ncol, 
     p.til_col = (int64_t)c->til_col; p.phi_col = (int64_t)c->phi_col; p.sca_col = (int64_t)c->sca_col;
     p.wavelength = c->d_wavelength; p.u_la = c->d_u_la; p.exp2_tab = c->d_exp2_tab; p.zmu = c->d_zmu; p.muz = c->d_muz; p.wmuh = c->d_wmuh;
     p.wl = c->d_wl; p.alpha = c->d_alpha; p.wnu = c->d_losses_wnu;
-    p.la_ptr = c->d_losses_ptr; p.ents = reinterpret_cast<const LossEnt*>(c->d_losses_ent); p.la_tile = c->d_losses_tile;
-    p.trans = c->d_trans; p.trans_row = c->d_losses_row; p.active = c->d_active;
+    p.la_ptr = c->d_final_ptr; p.ents = c->d_final_ent; p.la_tile = c->d_final_tile;
+    p.trans = c->d_trans; p.trans_row = c->d_final_row; p.active = c->d_active;
     p.height = c->d_height; p.temperature = c->d_temperature; p.n = c->d_n; p.nsr = c->d_nsr; p.wphi = c->d_wphi;
     p.bgchi_T = c->d_bgchi; p.bgeta_T = c->d_bgeta; p.J_T = c->d_J[c->jcur];      // what lsx_get(LSX_J) returns at this moment
     p.E_T = c->d_E; p.sca = c->d_sca; p.phi_T = c->d_phi;

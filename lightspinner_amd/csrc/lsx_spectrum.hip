@@ -7,7 +7,7 @@
 //   rh_method.py:599-638           opacity, emissivity, source function, emergent value I[0] of the up-going ray
 //   rh_method.py:231-239           line profile of the up-going ray at a wavelength and an angle
 //   rh_method.py:281-287, 453      continua: Vij = alpha, gij = (nStar_i / nStar_j) exp(-hc / k lambda T), Uji = (2hc / lambda^3) Vji
-//   formal_solver.py:46-142, 203-207   the recurrence with its end-point quirk, thermalised lower boundary
+// (the recurrence, its start value, the constants and planck: lsx_final_dev.h)
 //
 // Mapping (that of k_emergent_rays, lsx_rays.hip): one wavefront = 64 consecutive wavelengths of the CALL of one column, a lane owns
 // one wavelength and carries a compile-time chunk of NM angles in registers.  What a wavelength sees does not change with depth --
@@ -19,8 +19,8 @@
 // transition), and -- with a background of the caller's -- one contiguous run per stream of the pass's transposed copy
 // ([column][k][wavelength], k_spectrum_transpose).  Line profiles are evaluated with the library's Voigt function at every (line
 // wavelength, depth, angle), once per depth where the column has no line-of-sight velocity.  The Boltzmann factor and the Planck
-// function are formed in the lane at the new wavelength.  The linear rule runs in the reference's own order of operations (two
-// divisions per step, no contraction), as lsx_depth.hip has it; the parabolic rule is the sweep's generic instance.
+// function are formed in the lane at the new wavelength.  The linear rule runs in the reference's own order of operations
+// (linear_step_ref), as in lsx_depth.hip; the parabolic rule is the sweep's generic instance.
 // One writer per value, fixed order of every sum: a result does not depend on the column's place, the column range, the cut into
 // passes, the other wavelengths or the other angles of the call.
 #include <hip/hip_runtime.h>
@@ -31,18 +31,13 @@
 #include <vector>
 
 #include "../../include/lsx_hip.h"
-#include "lsx_ctx.h"
+#include "lsx_final_host.h"
 #include "lsx_voigt.h"
 
 using namespace lsxd;
 
 namespace {
 
-constexpr double kCLight = 2.99792458E+08;
-constexpr double kHPlanck = 6.6260755E-34;
-constexpr double kKBoltzmann = 1.380658E-23;
-constexpr double kNM_TO_M = 1.0E-09;
-constexpr double kHC = kHPlanck * kCLight;
 constexpr size_t kWorkCapDefault = (size_t)256 << 20;      // bytes (include/lsx_hip_spectrum.h)
 constexpr size_t kLdsLimit = (size_t)64 << 10;             // a workgroup's LDS without opting in to more
 constexpr int kTrD = 4, kTrI = 4;                          // doubles / integers of a transition's constants
@@ -73,15 +68,6 @@ struct SpecParams {
     const double *xchi, *xeta, *xsca;
     double* out;
 };
-
-// utils.py:17-22 (as lsx_sweep.hip has it)
-__device__ __forceinline__ double planck(double temp, double wav)
-{
-    const double hc_Tkla = kHC / (kKBoltzmann * kNM_TO_M * wav) / temp;
-    const double x = kNM_TO_M * wav;
-    const double twohnu3_c2 = (2.0 * kHC) / (x * x * x);
-    return twohnu3_c2 / (exp(hc_Tkla) - 1.0);
-}
 
 // (1 - t) a + t b as two products and a sum, never contracted: the bits numpy gives, exact at t = 0 and t = 1
 __device__ __forceinline__ double lerp2(double a, double b, double t)
@@ -152,11 +138,8 @@ __global__ void __launch_bounds__(64) k_spectrum(const SpecParams p)
         mu[m] = p.mu[p.mu0 + m];
         zmu[m] = 1.0 / mu[m];
     }
-    // state of the recurrence per angle: linear rule chi_prev, S_prev, dtau_prev; parabolic rule the window (upwind, local, downwind)
-    // of the depth being finished
     double Iu[NM], c_k[NM], S_k[NM], c_u[NM], S_u[NM], dtau_prev[NM];
-#pragma unroll
-    for (int m = 0; m < NM; ++m) { Iu[m] = 0.0; c_k[m] = 1.0; S_k[m] = 0.0; c_u[m] = 1.0; S_u[m] = 0.0; dtau_prev[m] = 1.0; }
+    final_state_init(Iu, c_k, S_k, c_u, S_u, dtau_prev);
     double zk1 = 0.0, zk2 = 0.0;       // heights of the two depths below the current one
     const double B0 = planck(T[Ns - 2], wav), B1 = planck(T[Ns - 1], wav);
 
@@ -216,66 +199,23 @@ __global__ void __launch_bounds__(64) k_spectrum(const SpecParams p)
                 for (int m = 0; m < NM; ++m) { chi[m] += c1; eta[m] += h1; }
             }
         }
-        // ---- the up-going ray's recurrence at this depth ----
+        // ---- the up-going ray's recurrence at this depth (lsx_final_dev.h): the linear rule in the reference's own order, as
+        // lsx_depth.hip has it (the end point of a ray can be a heavy cancellation, where a shared reciprocal's 4e-15 shows); the
+        // start value belongs to the depth below (Iu is still 0 there) ----
+        if (s == 1 && !lower_zero) thermal_start(B1, B0, fabs(zk1 - zk), zmu, c_k, chi, Iu);
+        double S[NM];
+#pragma unroll
+        for (int m = 0; m < NM; ++m) S[m] = eta[m] / chi[m];                       // :632
         if constexpr (!PAR) {
-            // formal_solver.py:107-139 operation by operation, in the reference's order and without contraction into fused
-            // multiply-adds: two divisions per step (lsx_depth.hip: the end point of a ray can be a heavy cancellation, where a shared
-            // reciprocal's 4e-15 shows)
-#pragma clang fp contract(off)
-            const double adz = fabs(zk1 - zk);
-#pragma unroll
-            for (int m = 0; m < NM; ++m) {
-                const double S = eta[m] / chi[m];                                   // :632
-                if (s == 0) {
-                    S_k[m] = S;
-                    c_k[m] = chi[m];
-                    continue;
-                }
-                if (s == 1) {                                      // thermalised lower boundary, formal_solver.py:203-207
-                    const double dtau_uw = zmu[m] * (c_k[m] + chi[m]) * 0.5 * adz;
-                    Iu[m] = lower_zero ? 0.0 : B1 - (B0 - B1) / dtau_uw;
-                }
-                const double dtau = 0.5 * (c_k[m] + chi[m]) * zmu[m] * adz;         // :107, :129
-                const double dS = (S_k[m] - S) / dtau;                              // :111, :130
-                // formal_solver.py:138-139: the end point re-uses the previous interval's w and S[kEnd - dk] with the fresh dS
-                const bool last = k == 0;
-                double w0, w1;
-                w2(last ? dtau_prev[m] : dtau, w0, w1, etab);
-                const double Sx = last ? S_k[m] : S;
-                Iu[m] = Iu[m] * (1.0 - w0) + w0 * Sx + w1 * dS;                     // :126
-                dtau_prev[m] = dtau;
-                c_k[m] = chi[m];
-                S_k[m] = S;
-            }
+            linear_step_ref(s, k == 0, fabs(zk1 - zk), zmu, chi, S, Iu, c_k, S_k, dtau_prev, etab);
         } else {
-            // monotonic parabolic rule (include/lsx.h, N4) as the sweep's generic instance: a depth is finished when its downwind
-            // neighbour is known.  Window after the shift: u = k + 2, k = k + 1, d = this depth
 #pragma unroll
-            for (int m = 0; m < NM; ++m) {
-                const double c_d = chi[m], S_d = eta[m] / chi[m];
-                if (s == 1) {
-                    const double dtau_uw = zmu[m] * (c_k[m] + c_d) * 0.5 * fabs(zk1 - zk);
-                    Iu[m] = lower_zero ? 0.0 : B1 - (B0 - B1) / dtau_uw;
-                }
-                if (s >= 2) {
-                    const double dtau_u = (c_u[m] + c_k[m]) * (0.5 * fabs(zk2 - zk1)) * zmu[m];
-                    const double dtau_d = (c_k[m] + c_d) * (0.5 * fabs(zk1 - zk)) * zmu[m];
-                    Iu[m] = parabolic_point(Iu[m], S_u[m], S_k[m], S_d, dtau_u, dtau_d, true, etab).I;
-                }
-                c_u[m] = c_k[m]; S_u[m] = S_k[m];
-                c_k[m] = c_d; S_k[m] = S_d;
-            }
+            for (int m = 0; m < NM; ++m) parabolic_step(s, zk, zk1, zk2, zmu[m], chi[m], S[m], Iu[m], c_k[m], S_k[m], c_u[m], S_u[m], etab);
         }
         zk2 = zk1;
         zk1 = zk;
     }
-    if constexpr (PAR) {            // the end point: no downwind neighbour (the linear rule with its own interval's weights)
-#pragma unroll
-        for (int m = 0; m < NM; ++m) {
-            const double dtau_u = (c_u[m] + c_k[m]) * (0.5 * fabs(zk2 - zk1)) * zmu[m];
-            Iu[m] = parabolic_point(Iu[m], S_u[m], S_k[m], 0.0, dtau_u, 1.0, false, etab).I;
-        }
-    }
+    if constexpr (PAR) parabolic_end(zk1, zk2, zmu, Iu, c_k, S_k, c_u, S_u, etab);
     if (valid) {
         double* o = p.out + ((size_t)blockIdx.y * p.nla + q) * p.nmu + p.mu0;    // emergent value I[0], rh_method.py:638
 #pragma unroll
@@ -422,11 +362,9 @@ extern "C" int lsx_hip_spectrum(lsx_ctx* c, int32_t nla, const double* wavelengt
         if (q && !(wavelength[q] > wavelength[q - 1]))
             return fail(LSX_EINVAL, "lsx_hip_spectrum: the wavelengths are not strictly ascending at [%d]", q);
     }
-    if (nmu < 1) return fail(LSX_EINVAL, "lsx_hip_spectrum: nmu = %d, need at least one angle", (int)nmu);
-    for (int m = 0; m < nmu; ++m)
-        if (!(mu[m] > 0.0 && mu[m] <= 1.0)) return fail(LSX_EINVAL, "lsx_hip_spectrum: mu[%d] = %g is outside (0, 1]", m, mu[m]);
-    if (col0 < 0 || ncol < 1 || (int64_t)col0 + ncol > c->ncol)
-        return fail(LSX_EINVAL, "lsx_hip_spectrum: columns [%d, %d) are outside the context's %d", (int)col0, (int)col0 + (int)ncol, c->ncol);
+    int rc = final_check_angles("lsx_hip_spectrum", nmu, mu);
+    if (!rc) rc = final_check_range(c, "lsx_hip_spectrum", col0, ncol);
+    if (rc) return rc;
     const size_t per = (size_t)nla * nmu;
     if (nbytes != (size_t)ncol * per * 8) return fail(LSX_EINVAL, "lsx_hip_spectrum: nbytes does not match [ncol][nla][nmu]");
     if ((bg_chi == nullptr) != (bg_eta == nullptr))
@@ -437,22 +375,10 @@ extern "C" int lsx_hip_spectrum(lsx_ctx* c, int32_t nla, const double* wavelengt
         return fail(LSX_EINVAL, "lsx_hip_spectrum: bg_sca is %s", want_sca ? "needed: the context's scattering coefficient is per wavelength"
                                                                            : "given, but only read next to bg_chi in a sca_per_lambda context");
     if (c->Ncont > 0 && !alpha) return fail(LSX_EINVAL, "lsx_hip_spectrum: alpha is NULL and the context has %d continua", c->Ncont);
-    if (c->Nspace < 3) return fail(LSX_EUNSUPPORTED, "lsx_hip_spectrum: needs Nspace >= 3");
-    for (int q = col0; q < col0 + ncol; ++q) {
-        if (!c->bnd_kind.empty() && c->bnd_kind[2 * (size_t)q] == LSX_BOUNDARY_GIVEN)
-            return fail(LSX_EUNSUPPORTED, "lsx_hip_spectrum: column %d has a GIVEN lower boundary (lsx_hip_set_boundary): its intensity was handed "
-                                          "over on the context's own rays and wavelengths and is not known at another angle or wavelength", q);
-        if (!c->phi_set[q])
-            return fail(LSX_EINVAL, "lsx_hip_spectrum: column %d has no line profiles (lsx_set_columns with phi == NULL must be "
-                                    "followed by lsx_set_line_profiles)", q);
-        if (c->Nlines && (c->prof_kind.empty() || !c->prof_kind[q]))
-            return fail(LSX_EUNSUPPORTED, "lsx_hip_spectrum: the line profiles of column %d were handed over as arrays "
-                                          "(lsx_set_columns): the library cannot know them at another wavelength.  Build them with "
-                                          "lsx_set_line_profiles or lsx_set_atmosphere", q);
-    }
+    if ((rc = final_check_depths(c, "lsx_hip_spectrum"))) return rc;
+    if ((rc = final_check_columns(c, "lsx_hip_spectrum", col0, ncol, FINAL_OTHER_WAVELENGTH))) return rc;
     SpecTables S;
-    int rc = spec_tables(c, nla, wavelength, alpha, &S);
-    if (rc) return rc;
+    if ((rc = spec_tables(c, nla, wavelength, alpha, &S))) return rc;
     const size_t lds = ((size_t)S.Emax * 64 + (size_t)c->Ntrans * 4) * (sizeof(double) + sizeof(int32_t));
     if (lds + (LSX_EXP_TAB + 64) * sizeof(double) > kLdsLimit)
         return fail(LSX_EUNSUPPORTED, "lsx_hip_spectrum: %d transitions overlap at one wavelength: their tables (%zu bytes) do not fit "
