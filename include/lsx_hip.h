@@ -81,5 +81,6 @@ int lsx_hip_poison_lds(int32_t device, int32_t rounds);
 #include "lsx_hip_timedep.h"
 #include "lsx_hip_epilogue.h"
 #include "lsx_hip_boundary.h"
+#include "lsx_hip_stokes.h"
 
 #endif /* LSX_HIP_H */

@@ -242,6 +242,14 @@ class LsxLibrary:
             d.lsx_hip_spectrum.restype = C.c_int
             d.lsx_hip_spectrum_work_cap.argtypes = [C.c_void_p, C.c_size_t]
             d.lsx_hip_spectrum_work_cap.restype = C.c_int
+        self.has_stokes = hasattr(d, 'lsx_hip_stokes_rays')            # include/lsx_hip_stokes.h
+        if self.has_stokes:
+            ip32 = C.POINTER(C.c_int32)
+            d.lsx_hip_stokes_rays.argtypes = [C.c_void_p, C.c_int32, _dp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp,
+                                              ip32, ip32, _dp, _dp, _dp, C.c_size_t]
+            d.lsx_hip_stokes_rays.restype = C.c_int
+            d.lsx_hip_stokes_rays_work_cap.argtypes = [C.c_void_p, C.c_size_t]
+            d.lsx_hip_stokes_rays_work_cap.restype = C.c_int
         self.has_background = hasattr(d, 'lsx_hip_background')         # include/lsx_hip_background.h
         if self.has_background:
             ip32 = C.POINTER(C.c_int32)

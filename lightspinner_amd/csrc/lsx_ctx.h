@@ -151,6 +151,12 @@ struct lsx_ctx : lsxd::LsxPlan {        // the plan (lsx_plan.h: dimensions, tab
     size_t spec_tab_bytes = 0;
     double* d_spec_work = nullptr;
     size_t spec_work_doubles = 0, spec_work_cap = 0;        // cap 0: the default of include/lsx_hip_spectrum.h
+    // ... and of lsx_hip_stokes_rays (lsx_stokes.hip): the Zeeman pattern tables of a call (rebuilt per call, the buffer grows as
+    // needed) and the angles, the field and the result of a pass (allocated at first use, under stokes_work_cap bytes)
+    char* d_stokes_tab = nullptr;
+    size_t stokes_tab_bytes = 0;
+    double* d_stokes_work = nullptr;
+    size_t stokes_work_doubles = 0, stokes_work_cap = 0;    // cap 0: the default of include/lsx_hip_stokes.h
     // Ng acceleration of the populations (lsx_ng.hip, include/lsx_hip_ng.h): off (order 0) unless lsx_hip_ng_configure turns it on
     int ng_order = 0, ng_delay = 0;
     double* d_ng_hist = nullptr;         // [col][order + 2][NLtot][k]: the stored populations, slot = the column's counter

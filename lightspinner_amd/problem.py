@@ -249,6 +249,17 @@ class DepthRays:
         self.chi, self.S, self.tau, self.I, self.contrib, self.z_tau1 = chi, S, tau, I, contrib, z_tau1
 
 
+class StokesRays:
+    """What Engine.stokes_rays returns: .I, .Q, .U, .V, each [ncol][nla][nmu], the emergent Stokes parameters of the up-going rays with
+    direction cosines .mus at the wavelengths [.la0, .la0 + nla) of the merged grid.  Context.compute_stokes drops the column axis (and
+    the angle axis for a scalar mu).  Definitions, the reference direction of +Q and the sign of V: include/lsx_hip_stokes.h."""
+    FIELDS = ('I', 'Q', 'U', 'V')
+
+    def __init__(self, mus, la0, I, Q, U, V):
+        self.mus, self.la0 = mus, int(la0)
+        self.I, self.Q, self.U, self.V = I, Q, U, V
+
+
 class NgOptions:
     """Ng acceleration of the MALI loop (include/lsx_hip_ng.h): order 1 or 2 (0: off), delay >= 0 statistical equilibria that pass
     before the first population vector is stored.  What Context(ng=...) and run_response_function(ng=...) take."""
@@ -637,6 +648,33 @@ class Engine:
         self.lib.check(self.lib.dll.lsx_hip_depth_rays(self._h, mu.shape[0], _ptr(mu), int(col0), ncol, int(la0), nla, *ptr,
                                                        int(np.prod(shape)) * 8, int(np.prod(shape[:2] + shape[3:])) * 8))
         return DepthRays(mu, la0, **out)
+
+    def stokes_rays(self, mus, B, gammaB, chiB, patterns=None, la0=0, nla=None, col0=0, ncol=None, work_cap_bytes=None):
+        """Emergent Stokes spectra in a magnetic field (Zeeman effect, field-free method: include/lsx_hip_stokes.h,
+        lsx_hip_stokes_rays) of the up-going rays with direction cosines `mus`, for columns [col0, col0 + ncol) and the wavelengths
+        [la0, la0 + nla) of the merged grid (nla None: to the end), from the current populations and J.  B [T], gammaB, chiB [rad]:
+        [ncol][Nspace] (a single column may be 1-D, a scalar holds everywhere): strength, inclination against the vertical, azimuth.
+        patterns: one entry per LINE of the problem in table order -- None (unpolarised), a zeeman.ZeemanComponents or an
+        (alpha, strength, shift) triple; None: no line is polarised.  work_cap_bytes: the cap of the pass's device memory from this
+        call on (None: unchanged; 0: the default).  Read-only.  -> StokesRays.  Only the HIP library computes it."""
+        from . import zeeman
+        if not getattr(self.lib, 'has_stokes', False):
+            raise NotImplementedError('%s (%s) does not export lsx_hip_stokes_rays: polarised spectra are computed by the HIP '
+                                      'library only' % (self.lib.path, self.lib.backend))
+        if work_cap_bytes is not None:
+            self.lib.check(self.lib.dll.lsx_hip_stokes_rays_work_cap(self._h, int(work_cap_bytes)))
+        mu = f64(np.atleast_1d(np.asarray(mus, dtype=np.float64)).reshape(-1))
+        ncol = self.ncol - int(col0) if ncol is None else int(ncol)
+        nla = self.problem.Nspect - int(la0) if nla is None else int(nla)
+        nc, Ns = max(ncol, 0), self.problem.Nspace
+        fld = [f64(np.broadcast_to(np.asarray(a, dtype=np.float64), (nc, Ns))) for a in (B, gammaB, chiB)]
+        ncomp, alpha, strength, shift = zeeman.pack(patterns, self.problem.Nlines)
+        out = np.empty((nc, 4, max(nla, 0), mu.shape[0]), dtype=np.float64)
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        self.lib.check(self.lib.dll.lsx_hip_stokes_rays(self._h, mu.shape[0], _ptr(mu), int(col0), ncol, int(la0), nla, _ptr(fld[0]),
+                                                        _ptr(fld[1]), _ptr(fld[2]), ip(ncomp), ip(alpha), _ptr(strength), _ptr(shift),
+                                                        _ptr(out), out.nbytes))
+        return StokesRays(mu, la0, out[:, 0], out[:, 1], out[:, 2], out[:, 3])
 
     def _background_lib(self, entry):
         if not getattr(self.lib, 'has_background', False):

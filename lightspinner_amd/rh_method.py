@@ -504,6 +504,29 @@ class Context:
         pick = (lambda a: a[0, 0]) if scalar else (lambda a: a[0])
         return DepthRays(r.mus, r.la0, **{w: pick(getattr(r, w)) for w in DepthRays.FIELDS})
 
+    def compute_stokes(self, mus, B, gammaB, chiB, transition=None, la0=0, nla=None):
+        """Emergent Stokes spectra I, Q, U, V in a magnetic field (Zeeman effect) by the field-free method: these populations and
+        this J, one polarised formal solution (DELO-linear) along the rays with direction cosines `mus`.  B [T], gammaB, chiB [rad]:
+        [Nspace] or scalars -- strength, inclination against the vertical, azimuth; +Q lies along the projection of the vertical
+        on the sky, a field pointing at the observer gives V > 0 on the blue flank of an absorption line (include/lsx_hip_stokes.h).
+        The Zeeman patterns come from the context's own line models (zeeman.zeeman_components: gLandeEff, or LS coupling from the
+        levels' J, L, S); a line without either stays unpolarised.  transition: one of the context's transitions (the object, or its
+        place in [t for atom in activeAtoms for t in atom.trans]) selects that transition's own window, as in compute_depth_rays.
+        -> an object with .I .Q .U .V, each [nla][nmu] ([nla] for a float mu), .mus, .la0.  Nothing of the context changes."""
+        from . import zeeman
+        from .problem import StokesRays
+        self._cancel_lookahead()                  # (the library's J is the last accepted call's again)
+        self._push_host_edits()
+        if transition is not None:
+            if isinstance(transition, (int, np.integer)):
+                transition = [t for a in self.activeAtoms for t in a.trans][int(transition)]
+            la0, nla = int(transition.Nblue), int(transition.wavelength.shape[0])
+        patterns = [zeeman.zeeman_components(t.transModel) for a in self.activeAtoms for t in a.trans if t.isLine]
+        scalar = np.ndim(mus) == 0
+        r = self._engine.stokes_rays(np.atleast_1d(np.asarray(mus, dtype=np.float64)), B, gammaB, chiB, patterns=patterns, la0=la0, nla=nla)
+        pick = (lambda a: a[0, :, 0]) if scalar else (lambda a: a[0])
+        return StokesRays(r.mus, r.la0, *(pick(getattr(r, w)) for w in StokesRays.FIELDS))
+
     def compute_rates(self):
         """Radiative rates of every transition (rh_method.py:691-692) as ONE formal solution gives them from these populations and
         this J: -> an object with .Rij, .Rji, .Rji_ref, each [Ntrans][Nspace] in the order of `.transitions`
