@@ -237,6 +237,11 @@ int background_from_device(lsx_ctx* c, size_t col0, size_t ncol, const double* d
 int profiles_from_device(lsx_ctx* c, size_t col0, size_t ncol, const double* dA, const double* dV, const double* dL);
 void profiles_handed_over(lsx_ctx* c, size_t col0, size_t ncol);    // these columns' profiles no longer come from kept inputs
 void mark_profiles_set(lsx_ctx* c, size_t col0, size_t ncol);
+// One solve of every atom's populations behind the last formal solution, on the context's stream (lsx_hip.hip): the statistical
+// equilibrium or the time-dependent step, which differ in the kernels that launch(c, atom, grid, block, lds) starts -- lds bytes
+// of LDS for the in-memory kernel, 0 for the register instance of the atom's level count.  Refuses (`what` names the caller)
+// before anything is launched; zeroes the monitors where the Gamma epilogue has not, enqueues Ng and marks the solve pending.
+int enqueue_solves(lsx_ctx* c, const char* what, void (*launch)(lsx_ctx*, int, dim3, dim3, size_t));
 // Ng acceleration (lsx_ng.hip); all three do nothing while it is off
 int ng_enqueue(lsx_ctx* c);                              // the step behind a statistical equilibrium, on the context's stream
 int ng_reset(lsx_ctx* c, size_t col0, size_t ncol);      // these columns' populations have been replaced: their history is discarded

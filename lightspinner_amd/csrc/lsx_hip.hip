@@ -20,6 +20,8 @@
 
 #include "lsx_ctx.h"
 #include "lsx_fast.h"
+#include "lsx_solve_dev.h"
+#include "lsx_solve_flag.h"
 #include "lsx_voigt.h"
 
 // A context launches up to six tile classes on streams of their own; with the HIP runtime's default of four hardware queues two
@@ -786,25 +788,8 @@ __global__ void __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(NLC ==
     fast_gamma_cols_rows<NLC, 6, 2, true>(f, f.fast_tiles[blockIdx.y], (long)blockIdx.x * 2 * LSX_FGC_ROWS, (long)f.ncol * f.Nspace, sm);
 }
 
-// singular system at (column, atom, depth): the flag keeps the FIRST one in that order, the one the reference raises on (it walks
-// the atoms outside the depths, rh_method.py:720-739, and the columns one after the other) -- one order-independent 64-bit
-// atomicMax of (2^48 - key), key = (column << 8 | atom) Nspace + depth, 0 = none -- for lsx_last_error (cf. LinAlgError)
-#define LSX_SING_BASE (1ull << 48)
-__device__ __forceinline__ void flag_singular(unsigned long long* flag, int col, int atom, int k, int Ns)
-{
-    atomicMax(flag, LSX_SING_BASE - ((((unsigned long long)col << 8) | (unsigned)atom) * (unsigned long long)Ns + (unsigned)k));
-}
-
-__device__ __forceinline__ void atomic_max_nonneg(double* addr, double v)
-{
-    // for non-negative doubles the IEEE bit pattern orders like the value
-    atomicMax(reinterpret_cast<unsigned long long*>(addr),
-              static_cast<unsigned long long>(__double_as_longlong(fabs(v))));
-}
-
-// rh_method.py:710-745.  One thread per (column, depth) of one atom; the Nl x Nl system of
-// each thread lives in a thread-private LDS column (A[e][tid]) -- dense LU with partial
-// pivoting in the operation order of LAPACK dgetf2/dgetrs.
+// rh_method.py:710-745.  One thread per (column, depth) of one atom; the Nl x Nl system of each thread lives in a thread-private
+// LDS column (lsx_solve_dev.h: solve_mem, the work entries blockDim.x apart).
 __global__ void k_stat_equil(const double* __restrict__ Gamma, const double* __restrict__ nTotal, double* __restrict__ n,
                              double* __restrict__ dPcol, unsigned long long* __restrict__ singular, int Nl, int lev_off, int lev2_off,
                              int atom, int Natoms, int NLtot, int NL2tot, int Ns, int ncol, const uint8_t* __restrict__ colmask)
@@ -815,65 +800,10 @@ __global__ void k_stat_equil(const double* __restrict__ Gamma, const double* __r
     if (gid >= (long)ncol * Ns) return;
     const int col = gid / Ns, k = gid % Ns;
     if (colmask && !colmask[col]) return;
-    double* A = sm + tid;                       // A[(i + j*Nl) * nt]
-    double* b = sm + (size_t)Nl * Nl * nt + tid; // b[i * nt]
-    double* nOld = b + (size_t)Nl * nt;
-    double* nk = n + ((size_t)col * NLtot + lev_off) * Ns + k;
-    const double* G = Gamma + ((size_t)col * NL2tot + lev2_off) * Ns + k;
-
-    int iE = 0;
-    double nmax = nk[0];
-    for (int l = 0; l < Nl; ++l) {
-        const double v = nk[(size_t)l * Ns];
-        nOld[l * nt] = v;
-        if (v > nmax) { nmax = v; iE = l; }      // np.argmax: first maximum
-    }
-    for (int i = 0; i < Nl; ++i)
-        for (int j = 0; j < Nl; ++j) A[(i + j * Nl) * nt] = (i == iE) ? 1.0 : G[(size_t)(i * Nl + j) * Ns];
-    for (int i = 0; i < Nl; ++i) b[i * nt] = 0.0;
-    b[iE * nt] = nTotal[((size_t)col * Natoms + atom) * Ns + k];
-
-    bool sing = false;
-    for (int j = 0; j < Nl && !sing; ++j) {
-        int pv = j;
-        double amax = fabs(A[(j + j * Nl) * nt]);
-        for (int i = j + 1; i < Nl; ++i) {
-            const double v = fabs(A[(i + j * Nl) * nt]);
-            if (v > amax) { amax = v; pv = i; }
-        }
-        if (A[(pv + j * Nl) * nt] == 0.0 || amax != amax) { sing = true; break; }
-        if (pv != j) {
-            for (int q = 0; q < Nl; ++q) {
-                const double t = A[(j + q * Nl) * nt];
-                A[(j + q * Nl) * nt] = A[(pv + q * Nl) * nt];
-                A[(pv + q * Nl) * nt] = t;
-            }
-            const double t = b[j * nt]; b[j * nt] = b[pv * nt]; b[pv * nt] = t;
-        }
-        const double r = 1.0 / A[(j + j * Nl) * nt];
-        for (int i = j + 1; i < Nl; ++i) A[(i + j * Nl) * nt] *= r;
-        for (int q = j + 1; q < Nl; ++q) {
-            const double ajq = A[(j + q * Nl) * nt];
-            for (int i = j + 1; i < Nl; ++i) A[(i + q * Nl) * nt] -= A[(i + j * Nl) * nt] * ajq;
-        }
-    }
-    if (sing) { flag_singular(singular, col, atom, k, Ns); return; }
-    for (int j = 0; j < Nl; ++j)
-        for (int i = j + 1; i < Nl; ++i) b[i * nt] -= A[(i + j * Nl) * nt] * b[j * nt];
-    for (int j = Nl - 1; j >= 0; --j) {
-        b[j * nt] /= A[(j + j * Nl) * nt];
-        for (int i = 0; i < j; ++i) b[i * nt] -= A[(i + j * Nl) * nt] * b[j * nt];
-    }
-    double mx = 0.0;
-    for (int i = 0; i < Nl; ++i) {
-        const double nn = b[i * nt];
-        const double ch = fabs(1.0 - nOld[i * nt] / nn);
-        mx = (ch != ch || mx != mx) ? __builtin_nan("") : fmax(mx, ch);   // change.max(): NaN wins inside one depth
-        nk[(size_t)i * Ns] = nn;
-    }
-    // maxRelChange = max(maxRelChange, change.max()) with Python's builtin max (rh_method.py:741): a NaN never
-    // replaces the running maximum, so a depth whose change is NaN drops out
-    if (mx == mx) atomic_max_nonneg(&dPcol[col], mx);
+    double mx;
+    const bool ok = lsxsolve::solve_mem(lsxsolve::StatEquil{nTotal + ((size_t)col * Natoms + atom) * Ns + k}, Nl, sm + tid, nt,
+                                        Gamma + ((size_t)col * NL2tot + lev2_off) * Ns + k, n + ((size_t)col * NLtot + lev_off) * Ns + k, Ns, &mx);
+    record_solve(ok, mx, singular, dPcol, col, atom, k, Ns);
 }
 
 // max over the context's columns of the per-column monitors (lsx_monitors): one block, fixed order
@@ -910,6 +840,11 @@ k_monitors(const double* __restrict__ res, int ncol, double* __restrict__ dst)
 // The same elimination with the system in registers: NL is a compile-time constant, every loop is unrolled and the
 // data-dependent row choices (the eliminated row, the pivot) become predicated selects.  Same operations in the same
 // order as k_stat_equil => identical results; used for the small atoms (NL <= 8) that stellar problems have.
+// This is lsxsolve::solve_reg<NL>(StatEquil) of lsx_solve_dev.h written out, and the one place where it still is: called as a
+// function, the compiler keeps the same arithmetic in 276 instead of 255 vector registers at NL = 8, one wave per SIMD instead
+// of two, and the solve of an 8-level atom takes 15 % longer.  A change to the elimination is made in both;
+// tests/test_stat_equil_systems.py holds the two to the same bits (the register instances against the LDS kernel, which calls
+// solve_mem, on the GPU; solve_reg against solve_mem on the CPU).
 template <int NL>
 __global__ void __launch_bounds__(64)
 k_stat_equil_reg(const double* __restrict__ Gamma, const double* __restrict__ nTotal, double* __restrict__ n,
@@ -1287,6 +1222,37 @@ void mark_profiles_set(lsx_ctx* c, size_t col0, size_t ncol)
         c->n_phi_set += (size_t)1 - c->phi_set[col0 + q];
         c->phi_set[col0 + q] = 1;
     }
+}
+
+int enqueue_solves(lsx_ctx* c, const char* what, void (*launch)(lsx_ctx*, int, dim3, dim3, size_t))
+{
+    c->spec_valid = false;            // the populations now build on the last formal solution
+    c->optab_fresh = false;           // the populations change (cleared FIRST: an early return below must not leave a stale table marked fresh;
+                                      // the table is rebuilt behind the read-back of this call's monitors: lsx_sync)
+    const int nt = 64;
+    const auto lds = [&](int a) -> size_t {     // 0: the atom runs a register instance
+        const bool reg = !c->opt_se_lds && lsxsolve::has_register_form(c->Nlevel[a]);
+        return reg ? 0 : lsxsolve::work_doubles(c->Nlevel[a]) * nt * sizeof(double);
+    };
+    for (int a = 0; a < c->Natoms; ++a)         // nothing is launched unless every atom's system can be: the call does not fail partway
+        if (lds(a) > 160 * 1024) return fail(LSX_EUNSUPPORTED, "%s: Nlevel = %d needs %zu B of LDS", what, c->Nlevel[a], lds(a));
+    HIPCHK(hipSetDevice(c->device));
+    // dPcol and the singular flag behind it start at zero: the Gamma epilogue of the formal solution has done that, unless this
+    // is a second solve on the same Gamma
+    if (!c->dp_zeroed) HIPCHK(hipMemsetAsync(c->d_dPcol, 0, ((size_t)c->ncol + 1) * 8, c->stream));
+    c->dp_zeroed = false;
+    const long nthreads = (long)c->ncol * c->Nspace;
+    for (int a = 0; a < c->Natoms; ++a) {
+        launch(c, a, dim3((unsigned)((nthreads + nt - 1) / nt)), dim3(nt), lds(a));
+        HIPCHK(hipGetLastError());
+    }
+    // Ng acceleration, where configured (lsx_ng.hip): one launch behind the solves, ahead of any read-back of this call's results
+    if (c->ng_order) {
+        const int rc = ng_enqueue(c);
+        if (rc) return rc;
+    }
+    c->se_pending = true;
+    return LSX_OK;
 }
 
 } // namespace lsxd
@@ -2059,47 +2025,18 @@ int lsx_discard_formal_sol(lsx_ctx* c)
 int lsx_stat_equil_async(lsx_ctx* c)
 {
     if (!c) return fail(LSX_EINVAL, "null ctx");
-    c->spec_valid = false;            // the populations now build on the last formal solution
-    c->optab_fresh = false;           // the populations change (cleared FIRST: an early return below must not leave a stale table marked fresh)
-    for (int a = 0; a < c->Natoms; ++a) {       // nothing is launched unless every atom's system can be: the call does not fail partway
-        const size_t sm = (size_t)(c->Nlevel[a] * c->Nlevel[a] + 2 * c->Nlevel[a]) * 64 * sizeof(double);
-        if ((c->opt_se_lds || c->Nlevel[a] > 8) && sm > 160 * 1024)
-            return fail(LSX_EUNSUPPORTED, "stat_equil: Nlevel = %d needs %zu B of LDS", c->Nlevel[a], sm);
-    }
-    HIPCHK(hipSetDevice(c->device));
-    // dPcol and the singular flag behind it start at zero: the Gamma epilogue of the formal solution has done that, unless
-    // this is a second stat_equil on the same Gamma
-    if (!c->dp_zeroed) HIPCHK(hipMemsetAsync(c->d_dPcol, 0, ((size_t)c->ncol + 1) * 8, c->stream));
-    c->dp_zeroed = false;
-    const long nthreads = (long)c->ncol * c->Nspace;
-    for (int a = 0; a < c->Natoms; ++a) {
-        const int Nl = c->Nlevel[a];
-        const int nt = 64;
-        const dim3 grid((unsigned)((nthreads + nt - 1) / nt));
-#define SE_REG(NLC) case NLC: hipLaunchKernelGGL((k_stat_equil_reg<NLC>), grid, dim3(nt), 0, c->stream, c->d_Gamma, c->d_nTotal, c->d_n, \
-                              c->d_dPcol, c->d_singular, c->lev_off[a], c->lev2_off[a], a, c->Natoms, c->NLtot, c->NL2tot,      \
-                              c->Nspace, c->ncol, c->d_colmask); break;
-        switch (c->opt_se_lds ? 0 : Nl) {
-        SE_REG(2) SE_REG(3) SE_REG(4) SE_REG(5) SE_REG(6) SE_REG(7) SE_REG(8)
-        default: {
-            const size_t sm = (size_t)(Nl * Nl + 2 * Nl) * nt * sizeof(double);
-            if (sm > 160 * 1024) return fail(LSX_EUNSUPPORTED, "stat_equil: Nlevel = %d needs %zu B of LDS", Nl, sm);
-            hipLaunchKernelGGL(k_stat_equil, grid, dim3(nt), sm, c->stream, c->d_Gamma, c->d_nTotal, c->d_n, c->d_dPcol,
-                               c->d_singular, Nl, c->lev_off[a], c->lev2_off[a], a, c->Natoms, c->NLtot, c->NL2tot, c->Nspace,
-                               c->ncol, c->d_colmask);
-        }
-        }
-#undef SE_REG
-        HIPCHK(hipGetLastError());
-    }
-    // Ng acceleration, where configured (lsx_ng.hip): one launch behind the solves, ahead of any read-back of this call's results
-    if (c->ng_order) {
-        const int rc = ng_enqueue(c);
-        if (rc) return rc;
-    }
-    c->se_pending = true;
-    c->optab_fresh = false;           // the populations have changed (the table is rebuilt behind the read-back of this call's monitors: lsx_sync)
-    return LSX_OK;
+    return enqueue_solves(c, "stat_equil", [](lsx_ctx* c, int a, dim3 grid, dim3 block, size_t lds) {
+        if (lds)
+            hipLaunchKernelGGL(k_stat_equil, grid, block, lds, c->stream, c->d_Gamma, c->d_nTotal, c->d_n, c->d_dPcol, c->d_singular,
+                               c->Nlevel[a], c->lev_off[a], c->lev2_off[a], a, c->Natoms, c->NLtot, c->NL2tot, c->Nspace, c->ncol,
+                               c->d_colmask);
+        else
+            lsxsolve::with_register_form(c->Nlevel[a], [&](auto nl) {
+                hipLaunchKernelGGL((k_stat_equil_reg<decltype(nl)::value>), grid, block, 0, c->stream, c->d_Gamma, c->d_nTotal, c->d_n,
+                                   c->d_dPcol, c->d_singular, c->lev_off[a], c->lev2_off[a], a, c->Natoms, c->NLtot, c->NL2tot,
+                                   c->Nspace, c->ncol, c->d_colmask);
+            });
+    });
 }
 
 int lsx_set_active_columns(lsx_ctx* c, const uint8_t* active)
@@ -2237,7 +2174,7 @@ int lsx_sync(lsx_ctx* c, double* dJ, double* dP)
 
 static int singular_error(lsx_ctx* c, unsigned long long sing)
 {
-    const unsigned long long key = LSX_SING_BASE - sing, ca = key / (unsigned long long)c->Nspace;      // flag_singular
+    const unsigned long long key = kSingBase - sing, ca = key / (unsigned long long)c->Nspace;      // flag_singular
     return fail(LSX_ESINGULAR, "stat_equil: singular matrix at column %ld, depth %ld, atom %d (the first such system; cf. "
                                "LinAlgError at rh_method.py:739); its populations are left untouched",
                 (long)(ca >> 8), (long)(key % (unsigned long long)c->Nspace), (int)(ca & 0xff));

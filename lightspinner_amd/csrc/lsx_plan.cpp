@@ -6,6 +6,7 @@
 //   rh_method.py:451, 455  wla = wlambda wphi / hc (lines), wlambda / lambda / h (continua)
 //   atomic_set.py:412-424  [Nblue, Nblue + Nlambda) and the `active` table the plan groups wavelengths by
 #include "lsx_plan.h"
+#include "lsx_solve_dev.h"
 
 #include <algorithm>
 #include <cmath>
@@ -538,10 +539,10 @@ int plan_build(const lsx_problem* d, const PlanOptions& opt, LsxPlan* out, std::
     S.finish_lds = nl2max * S.finish_nt * sizeof(double);
     }
     if (S.finish_lds > 64 * 1024) return perr(err, LSX_EUNSUPPORTED, "lsx_create: the Gamma epilogue needs %zu B of LDS", S.finish_lds);
-    for (int a = 0; a < P.Natoms; ++a) {       // k_stat_equil: atoms with more than 8 levels keep their system in LDS
+    for (int a = 0; a < P.Natoms; ++a) {       // the solves (lsx_solve_dev.h): atoms with more than 8 levels keep their system in LDS, 64 threads a workgroup
         const int Nl = P.Nlevel[a];
-        if (Nl > 8 && (size_t)(Nl * Nl + 2 * Nl) * 64 * sizeof(double) > 160 * 1024)
-            return perr(err, LSX_EUNSUPPORTED, "lsx_create: stat_equil with Nlevel = %d needs %zu B of LDS", Nl, (size_t)(Nl * Nl + 2 * Nl) * 64 * sizeof(double));
+        const size_t lds = lsxsolve::work_doubles(Nl) * 64 * sizeof(double);
+        if (Nl > 8 && lds > 160 * 1024) return perr(err, LSX_EUNSUPPORTED, "lsx_create: stat_equil with Nlevel = %d needs %zu B of LDS", Nl, lds);
     }
     // the fused small-batch launch (and the parabolic rule): one kernel for every tile
     for (auto& k : P.plan_classes) { S.fused_ncell_lev = std::max(S.fused_ncell_lev, k.ncell_lev); S.fused_ncell_atom = std::max(S.fused_ncell_atom, k.ncell_atom); }

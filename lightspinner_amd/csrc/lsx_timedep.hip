@@ -2,11 +2,11 @@
 // depth, on the device (include/lsx_hip_timedep.h: the scheme and the entries).  Unused unless lsx_hip_time_dep_start is called;
 // gfx950 only.
 //
-// The kernels are the statistical equilibrium's (lsx_hip.hip: k_stat_equil, k_stat_equil_reg) with another system assembled in
-// front of the same elimination: one thread per (column, depth) of one atom, the system in registers for 2 ... 8 levels and in
-// thread-private LDS columns above (or for every size under the option se_lds).  The formulas live in lsx_timedep_dev.h, which
-// the CPU tests compile for the host.  A thread reads and writes its own point only: a column's bits depend neither on the
-// context's column count nor on the column's index.
+// The kernels are the statistical equilibrium's (lsx_hip.hip: k_stat_equil, k_stat_equil_reg) with another system in front of the
+// one elimination both call (lsx_solve_dev.h, which the CPU tests compile for the host): one thread per (column, depth) of one
+// atom, the system in registers for 2 ... 8 levels and in thread-private LDS columns above (or for every size under the option
+// se_lds).  A thread reads and writes its own point only: a column's bits depend neither on the context's column count nor on
+// the column's index.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -15,25 +15,12 @@
 
 #include "../../include/lsx_hip.h"
 #include "lsx_ctx.h"
-#include "lsx_timedep_dev.h"
+#include "lsx_solve_dev.h"
+#include "lsx_solve_flag.h"
 
 using namespace lsxd;
 
 namespace {
-
-// the singular flag and the per-column monitor: the protocol of the statistical equilibrium (lsx_hip.hip: flag_singular,
-// atomic_max_nonneg), which lsx_sync / lsx_last_error decode -- keep the two in step
-constexpr unsigned long long kSingBase = 1ull << 48;
-__device__ __forceinline__ void td_flag_singular(unsigned long long* flag, int col, int atom, int k, int Ns)
-{
-    atomicMax(flag, kSingBase - ((((unsigned long long)col << 8) | (unsigned)atom) * (unsigned long long)Ns + (unsigned)k));
-}
-
-__device__ __forceinline__ void td_atomic_max_nonneg(double* addr, double v)
-{
-    // for non-negative doubles the IEEE bit pattern orders like the value
-    atomicMax(reinterpret_cast<unsigned long long*>(addr), static_cast<unsigned long long>(__double_as_longlong(fabs(v))));
-}
 
 struct TdParams {
     const double* Gamma;            // [col][NL2tot][k]
@@ -56,13 +43,9 @@ k_time_dep_reg(const TdParams p)
     if (p.colmask && !p.colmask[col]) return;
     const size_t o = ((size_t)col * p.NLtot + p.lev_off) * p.Ns + k;
     double ch;
-    if (!lsxtd::solve_reg<NL>(p.Gamma + ((size_t)col * p.NL2tot + p.lev2_off) * p.Ns + k, p.n_prev + o, p.n + o, (size_t)p.Ns,
-                              p.dt[col], &ch)) {
-        td_flag_singular(p.singular, col, p.atom, k, p.Ns);
-        return;
-    }
-    // the maximum over depths drops a NaN, as the statistical equilibrium's does (rh_method.py:741)
-    if (ch == ch) td_atomic_max_nonneg(&p.dPcol[col], ch);
+    const bool ok = lsxsolve::solve_reg<NL>(lsxsolve::TimeStep{p.dt[col], p.n_prev + o, p.Ns},
+                                            p.Gamma + ((size_t)col * p.NL2tot + p.lev2_off) * p.Ns + k, p.n + o, p.Ns, &ch);
+    record_solve(ok, ch, p.singular, p.dPcol, col, p.atom, k, p.Ns);
 }
 
 __global__ void __launch_bounds__(64)
@@ -76,15 +59,10 @@ k_time_dep(const TdParams p, int Nl)
     if (p.colmask && !p.colmask[col]) return;
     const size_t o = ((size_t)col * p.NLtot + p.lev_off) * p.Ns + k;
     double ch;
-    if (!lsxtd::solve_mem(Nl, sm + tid, (size_t)nt, p.Gamma + ((size_t)col * p.NL2tot + p.lev2_off) * p.Ns + k, p.n_prev + o,
-                          p.n + o, (size_t)p.Ns, p.dt[col], &ch)) {
-        td_flag_singular(p.singular, col, p.atom, k, p.Ns);
-        return;
-    }
-    if (ch == ch) td_atomic_max_nonneg(&p.dPcol[col], ch);
+    const bool ok = lsxsolve::solve_mem(lsxsolve::TimeStep{p.dt[col], p.n_prev + o, p.Ns}, Nl, sm + tid, nt,
+                                        p.Gamma + ((size_t)col * p.NL2tot + p.lev2_off) * p.Ns + k, p.n + o, p.Ns, &ch);
+    record_solve(ok, ch, p.singular, p.dPcol, col, p.atom, k, p.Ns);
 }
-
-size_t lds_bytes(int Nl) { return lsxtd::work_doubles(Nl) * 64 * sizeof(double); }
 
 int ensure_state(lsx_ctx* c)
 {
@@ -146,44 +124,18 @@ extern "C" int lsx_hip_time_dep_start(lsx_ctx* c, int32_t col0, int32_t ncol, co
 extern "C" int lsx_hip_time_dep_update_async(lsx_ctx* c)
 {
     if (!c) return fail(LSX_EINVAL, "lsx_hip_time_dep_update_async: null context");
-    // nothing is touched or launched unless every active column has a step and every atom's system can be solved
+    // nothing is touched or launched unless every active column has a step
     for (int q = 0; q < c->ncol; ++q)
         if ((c->colmask_host.empty() || c->colmask_host[q]) && !(q < (int)c->td_dt.size() && c->td_dt[q] > 0.0))
             return fail(LSX_EINVAL, "lsx_hip_time_dep_update: no step has been started for column %d (lsx_hip_time_dep_start)", q);
-    for (int a = 0; a < c->Natoms; ++a)
-        if ((c->opt_se_lds || c->Nlevel[a] > 8) && lds_bytes(c->Nlevel[a]) > 160 * 1024)
-            return fail(LSX_EUNSUPPORTED, "time_dep_update: Nlevel = %d needs %zu B of LDS", c->Nlevel[a], lds_bytes(c->Nlevel[a]));
-    c->spec_valid = false;            // the populations now build on the last formal solution
-    c->optab_fresh = false;           // the populations change
-    HIPCHK(hipSetDevice(c->device));
-    // dPcol and the singular flag behind it start at zero: the Gamma epilogue of the formal solution has done that, unless this
-    // is a second update on the same Gamma
-    if (!c->dp_zeroed) HIPCHK(hipMemsetAsync(c->d_dPcol, 0, ((size_t)c->ncol + 1) * 8, c->stream));
-    c->dp_zeroed = false;
-    const long nthreads = (long)c->ncol * c->Nspace;
-    const int nt = 64;
-    const dim3 grid((unsigned)((nthreads + nt - 1) / nt));
-    TdParams p;
-    p.Gamma = c->d_Gamma; p.n_prev = c->d_td_n_prev; p.dt = c->d_td_dt; p.n = c->d_n; p.dPcol = c->d_dPcol;
-    p.singular = c->d_singular; p.colmask = c->d_colmask; p.NLtot = c->NLtot; p.NL2tot = c->NL2tot; p.Ns = c->Nspace; p.ncol = c->ncol;
-    for (int a = 0; a < c->Natoms; ++a) {
-        const int Nl = c->Nlevel[a];
+    return enqueue_solves(c, "time_dep_update", [](lsx_ctx* c, int a, dim3 grid, dim3 block, size_t lds) {
+        TdParams p;
+        p.Gamma = c->d_Gamma; p.n_prev = c->d_td_n_prev; p.dt = c->d_td_dt; p.n = c->d_n; p.dPcol = c->d_dPcol;
+        p.singular = c->d_singular; p.colmask = c->d_colmask; p.NLtot = c->NLtot; p.NL2tot = c->NL2tot; p.Ns = c->Nspace; p.ncol = c->ncol;
         p.lev_off = c->lev_off[a]; p.lev2_off = c->lev2_off[a]; p.atom = a;
-#define TD_REG(NLC) case NLC: hipLaunchKernelGGL((k_time_dep_reg<NLC>), grid, dim3(nt), 0, c->stream, p); break;
-        switch (c->opt_se_lds ? 0 : Nl) {
-        TD_REG(2) TD_REG(3) TD_REG(4) TD_REG(5) TD_REG(6) TD_REG(7) TD_REG(8)
-        default: hipLaunchKernelGGL(k_time_dep, grid, dim3(nt), lds_bytes(Nl), c->stream, p, Nl);
-        }
-#undef TD_REG
-        HIPCHK(hipGetLastError());
-    }
-    // Ng acceleration, where configured (lsx_ng.hip): one launch behind the solves, ahead of any read-back of this call's results
-    if (c->ng_order) {
-        const int rc = ng_enqueue(c);
-        if (rc) return rc;
-    }
-    c->se_pending = true;
-    return LSX_OK;
+        if (lds) hipLaunchKernelGGL(k_time_dep, grid, block, lds, c->stream, p, c->Nlevel[a]);
+        else lsxsolve::with_register_form(c->Nlevel[a], [&](auto nl) { hipLaunchKernelGGL((k_time_dep_reg<decltype(nl)::value>), grid, block, 0, c->stream, p); });
+    });
 }
 
 extern "C" int lsx_hip_time_dep_update(lsx_ctx* c, double* dPops_max)

@@ -1,8 +1,9 @@
-// lsx_timedep_san_main.cpp -- a stand-alone program (`make tdsan`) that runs the implicit rate-equation step of lsx_timedep_dev.h
-// through the entry of lsx_timedep_host.cpp, built with -fsanitize=address,undefined (tests/test_time_dependent_host.py runs it as
-// a subprocess): 13 depths x 25 columns = 325 systems of every size 2 ... 16, rates over twelve decades, dt over sixteen, in the
-// register form and the in-memory form (work strides 1 and 64), one frozen column, one singular and one NaN system, and the
-// refusals.  Each result must be finite and positive, conserve the number density, and agree between the two forms bit for bit.
+// lsx_timedep_san_main.cpp -- a stand-alone program (`make tdsan`) that runs the solve of lsx_solve_dev.h through the entries of
+// lsx_timedep_host.cpp -- the implicit rate-equation step, then the statistical equilibrium -- built with
+// -fsanitize=address,undefined (tests/test_time_dependent_host.py runs it as a subprocess): 13 depths x 25 columns = 325 systems
+// of every size 2 ... 16, rates over twelve decades, dt over sixteen, in the register form and the in-memory form (work strides 1
+// and 64), one frozen column, one singular and one NaN system, and the refusals.  Each result must be finite and positive,
+// conserve the number density (the step: the sum of n_prev; the equilibrium: nTotal), and agree between the two forms bit for bit.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -11,6 +12,8 @@
 
 extern "C" int lsx_timedep_host(int32_t, int32_t, int32_t, const double*, const double*, const double*, double*, double*, uint8_t*,
                                 const uint8_t*, int32_t, int32_t);
+extern "C" int lsx_statequil_host(int32_t, int32_t, int32_t, const double*, const double*, double*, double*, uint8_t*, const uint8_t*,
+                                  int32_t, int32_t);
 
 static uint64_t g_state = 0x9e3779b97f4a7c15ull;
 static double uniform()         // xorshift64*: [0, 1)
@@ -19,7 +22,8 @@ static double uniform()         // xorshift64*: [0, 1)
     return (double)((g_state * 0x2545f4914f6cdd1dull) >> 11) * (1.0 / 9007199254740992.0);
 }
 
-static int run(int Nl)
+// se: the statistical equilibrium on the same systems (np[level 0] of a point stands in for its nTotal)
+static int run(int Nl, bool se)
 {
     const int Ns = 13, nc = 25, sc = 7, sk = 5, nanc = 11, nank = 2, frozen = 19;
     const size_t per = (size_t)Nl * Ns;
@@ -42,10 +46,11 @@ static int run(int Nl)
             }
         }
     }
-    // a singular system: Gamma = I / dt (dt a power of two: exact) leaves rows of zeros beside the row of ones
+    // a singular system: Gamma = I / dt (dt a power of two: exact), for the equilibrium Gamma = 0, leaves rows of zeros beside
+    // the row of ones
     dt[sc] = 0.25;
     for (int i = 0; i < Nl; ++i)
-        for (int j = 0; j < Nl; ++j) G[(size_t)sc * Nl * Nl * Ns + (size_t)(i * Nl + j) * Ns + sk] = i == j ? 1.0 / dt[sc] : 0.0;
+        for (int j = 0; j < Nl; ++j) G[(size_t)sc * Nl * Nl * Ns + (size_t)(i * Nl + j) * Ns + sk] = i == j && !se ? 1.0 / dt[sc] : 0.0;
     G[(size_t)nanc * Nl * Nl * Ns + (size_t)(1 * Nl + 0) * Ns + nank] = NAN;
     G[(size_t)nanc * Nl * Nl * Ns + (size_t)(0 * Nl + 0) * Ns + nank] = NAN;
 
@@ -56,8 +61,14 @@ static int run(int Nl)
         out[f] = n0;
         dP[f].assign(nc, -1.0);
         std::vector<uint8_t> sing((size_t)nc * Ns, 9);
-        if (lsx_timedep_host(Nl, Ns, nc, G.data(), np.data(), dt.data(), out[f].data(), dP[f].data(), sing.data(), active.data(),
-                             forms[f][0], forms[f][1])) { fprintf(stderr, "Nl %d: refused\n", Nl); return 1; }
+        // (the equilibrium's nTotal [nc][Ns]: the first Ns entries of each column of np, i.e. level 0)
+        std::vector<double> ntot((size_t)nc * Ns);
+        for (int c = 0; c < nc; ++c) memcpy(&ntot[(size_t)c * Ns], &np[c * per], Ns * sizeof(double));
+        const int rc = se ? lsx_statequil_host(Nl, Ns, nc, G.data(), ntot.data(), out[f].data(), dP[f].data(), sing.data(), active.data(),
+                                               forms[f][0], forms[f][1])
+                          : lsx_timedep_host(Nl, Ns, nc, G.data(), np.data(), dt.data(), out[f].data(), dP[f].data(), sing.data(),
+                                             active.data(), forms[f][0], forms[f][1]);
+        if (rc) { fprintf(stderr, "Nl %d: refused\n", Nl); return 1; }
         for (int c = 0; c < nc; ++c)
             for (int k = 0; k < Ns; ++k) {
                 const bool want_sing = (c == sc && k == sk) || (c == nanc && k == nank);
@@ -74,7 +85,8 @@ static int run(int Nl)
                     sum += v;
                     want += np[e];
                 }
-                if (std::fabs(sum - want) > 1e-9 * want) { fprintf(stderr, "Nl %d form %d: (%d, %d): %.17g levels sum, %.17g before\n", Nl, f, c, k, sum, want); return 1; }
+                if (se && c != frozen && !want_sing) want = ntot[(size_t)c * Ns + k];
+                if (std::fabs(sum - want) > 1e-9 * want) { fprintf(stderr, "Nl %d form %d: (%d, %d): %.17g levels sum, %.17g wanted\n", Nl, f, c, k, sum, want); return 1; }
             }
         if (dP[f][frozen] != 0.0) { fprintf(stderr, "Nl %d form %d: monitor of the frozen column\n", Nl, f); return 1; }
         for (int c = 0; c < nc; ++c)
@@ -91,8 +103,9 @@ static int run(int Nl)
 
 int main()
 {
-    for (int Nl = 2; Nl <= 16; ++Nl)
-        if (run(Nl)) return 1;
+    for (int se = 0; se < 2; ++se)
+        for (int Nl = 2; Nl <= 16; ++Nl)
+            if (run(Nl, se != 0)) return 1;
     // refusals: nothing is read past what the checks allow
     std::vector<double> x(2 * 2 * 3, 1.0), dt(1, 1.0), dp(1);
     std::vector<uint8_t> s(3);
@@ -105,7 +118,12 @@ int main()
         dt[0] = bad;
         refused += lsx_timedep_host(2, 3, 1, x.data(), x.data(), dt.data(), x.data(), dp.data(), s.data(), nullptr, 0, 1) == 1;
     }
-    if (refused != 8) { fprintf(stderr, "%d of 8 refusals\n", refused); return 1; }
+    dt[0] = 1.0;
+    refused += lsx_statequil_host(1, 3, 1, x.data(), x.data(), x.data(), dp.data(), s.data(), nullptr, 0, 1) == 1;
+    refused += lsx_statequil_host(17, 3, 1, x.data(), x.data(), x.data(), dp.data(), s.data(), nullptr, 0, 1) == 1;
+    refused += lsx_statequil_host(2, 3, 1, x.data(), nullptr, x.data(), dp.data(), s.data(), nullptr, 0, 1) == 1;
+    refused += lsx_statequil_host(2, 3, 1, x.data(), x.data(), x.data(), dp.data(), s.data(), nullptr, 0, 0) == 1;
+    if (refused != 12) { fprintf(stderr, "%d of 12 refusals\n", refused); return 1; }
     printf("TIMEDEP SANITIZED RUN COMPLETE\n");
     return 0;
 }

@@ -156,8 +156,19 @@ def family_inputs(family, prob, block, a, seed, ntot_factor=0.3):
 
 
 # ---- the exact reference and its bars ---------------------------------------------------------------------------------------
+_exact_cache = {}
+
+
 def exact_system(G, n_old, nTot):
-    """one system: G [Nl][Nl] read back from the library, n_old [Nl] -> (x as mpmath numbers, bar [Nl], A, pivot rows)"""
+    """one system: G [Nl][Nl] read back from the library, n_old [Nl] -> (x as mpmath numbers, bar [Nl], pivot rows).  Kept per
+    input: the oracle's run and the host build's solve the same systems"""
+    key = (np.ascontiguousarray(G).tobytes(), np.ascontiguousarray(n_old).tobytes(), float(nTot))
+    if key not in _exact_cache:
+        _exact_cache[key] = _exact_system(G, n_old, nTot)
+    return _exact_cache[key]
+
+
+def _exact_system(G, n_old, nTot):
     Nl = G.shape[0]
     iE = int(np.argmax(n_old))
     A = np.array(G, dtype=np.float64)
@@ -415,6 +426,60 @@ def nan_in_the_rates(lib, Nl):
         check_solve(w, prob, G, n_old, e.get(_capi.LSX_N), block.nTotal, e.get(_capi.LSX_DPOPS_COL), singular={(sc, a, sk)})
         e.close()
     return w
+
+
+# ---- the host build of the device's solve (td_cases.HostLib) on the oracle's Gamma -------------------------------------------
+def oracle_gamma(oracle_lib, prob, block):
+    e = Engine(prob, block.ncol, lib=oracle_lib)
+    e.set_columns(0, block)
+    e.formal_sol_gamma()
+    G, n_old = e.get(_capi.LSX_GAMMA), e.get(_capi.LSX_N)
+    e.close()
+    return G, n_old
+
+
+def host_forms(host, prob, G, nTotal, n_old, Nl, singular=frozenset()):
+    """the form the device runs for this size; up to 8 levels, the in-memory form at work strides 1 and 64 gives its bits"""
+    n_new, dPcol, flagged = host.solve(prob, G, nTotal, n_old)
+    assert flagged == set(singular)
+    for stride in (1, 64) if Nl <= 8 else ():
+        n_mem, dP_mem, fl_mem = host.solve(prob, G, nTotal, n_old, in_memory=True, work_stride=stride)
+        assert np.array_equal(n_mem.view(np.uint64), n_new.view(np.uint64)), (Nl, stride)
+        assert np.array_equal(dP_mem.view(np.uint64), dPcol.view(np.uint64)), (Nl, stride)
+        assert fl_mem == flagged
+    return n_new, dPcol
+
+
+def host_family(oracle_lib, host, name, Nl):
+    """`family` with Gamma and n from the oracle's formal solution and the solve from the host build: the same inputs, the same
+    checker, the same bars"""
+    w = Worst('host %s Nl=%d' % (name, Nl))
+    for s, (Ns, nc) in enumerate(SHAPES):
+        prob, block, (a,) = probe_problem([Nl], Ns, nc)
+        family_inputs(name, prob, block, a, seed=1000 * Nl + s)
+        G, n_old = oracle_gamma(oracle_lib, prob, block)
+        n_new, dPcol = host_forms(host, prob, G, block.nTotal, n_old, Nl)
+        check_solve(w, prob, G, n_old, n_new, block.nTotal, dPcol)
+    w.report()
+    return w
+
+
+def host_bad_systems(oracle_lib, host, Nl):
+    """one singular system (its rates zeroed, as one_singular_system) and one with a NaN rate (as nan_in_the_rates) among regular
+    ones: both flagged and nothing else, their populations bit-identical to before, the others solved and monitored as usual"""
+    Ns, nc = SHAPES[1]
+    prob, block, (a,) = probe_problem([Nl], Ns, nc)
+    family_inputs('rate_scale', prob, block, a, seed=5)
+    bad = rates_of(prob, block.C, a).copy()
+    bad[3, :, :, 12] = 0.0
+    bad[2, Nl - 1, 0, 9] = np.nan
+    put(prob, block, a, C=bad)
+    G, n_old = oracle_gamma(oracle_lib, prob, block)
+    singular = {(3, a, 12), (2, a, 9)}
+    n_new, dPcol = host_forms(host, prob, G, block.nTotal, n_old, Nl, singular)
+    w = Worst('host bad systems Nl=%d' % Nl)
+    check_solve(w, prob, G, n_old, n_new, block.nTotal, dPcol, singular=singular)
+    w.report()
 
 
 # ---- 8, 9: HIP only ---------------------------------------------------------------------------------------------------------

@@ -221,13 +221,34 @@ def check_step(w, prob, G, n_prev, n_old, n_new, dt, dPcol, singular=(), active=
 
 # ---- runners: the HIP library on a GPU, or the oracle's Gamma through the host build of the formulas ---------------------
 class HostLib:
-    """liblsx_td_host.so (make tdhost): lsx_timedep_dev.h compiled for the CPU"""
+    """liblsx_td_host.so (make tdhost): lsx_solve_dev.h compiled for the CPU, the time-dependent step and the statistical equilibrium"""
     def __init__(self):
         subprocess.check_call(['make', '-s', '-C', CSRC, 'tdhost'])
         self.dll = C.CDLL(os.path.join(CSRC, 'liblsx_td_host.so'))
         dp, bp = C.POINTER(C.c_double), C.POINTER(C.c_uint8)
         self.dll.lsx_timedep_host.argtypes = [C.c_int32, C.c_int32, C.c_int32, dp, dp, dp, dp, dp, bp, bp, C.c_int32, C.c_int32]
         self.dll.lsx_timedep_host.restype = C.c_int
+        self.dll.lsx_statequil_host.argtypes = [C.c_int32, C.c_int32, C.c_int32, dp, dp, dp, dp, bp, bp, C.c_int32, C.c_int32]
+        self.dll.lsx_statequil_host.restype = C.c_int
+
+    def solve(self, prob, G, nTotal, n_old, active=None, in_memory=False, work_stride=1):
+        """the statistical equilibrium of every atom of every column -> (n_new, DPOPS_COL, {(col, atom, depth)} flagged)"""
+        dp, bp = C.POINTER(C.c_double), C.POINTER(C.c_uint8)
+        ncol, Ns = G.shape[0], prob.Nspace
+        n_new, dPcol, flagged = np.array(n_old), np.zeros(ncol), set()
+        act = None if active is None else np.ascontiguousarray(active, dtype=np.uint8)
+        for a in range(prob.Natoms):
+            Nl, o, o2 = prob.Nlevel[a], prob.lev_off[a], prob.lev2_off[a]
+            Ga, na = np.ascontiguousarray(G[:, o2:o2 + Nl * Nl]), np.ascontiguousarray(n_old[:, o:o + Nl])
+            nt, dP, sing = np.ascontiguousarray(nTotal[:, a], dtype=np.float64), np.zeros(ncol), np.zeros((ncol, Ns), dtype=np.uint8)
+            rc = self.dll.lsx_statequil_host(Nl, Ns, ncol, Ga.ctypes.data_as(dp), nt.ctypes.data_as(dp), na.ctypes.data_as(dp),
+                                             dP.ctypes.data_as(dp), sing.ctypes.data_as(bp),
+                                             None if act is None else act.ctypes.data_as(bp), int(in_memory), int(work_stride))
+            assert rc == 0
+            n_new[:, o:o + Nl] = na
+            dPcol = np.maximum(dPcol, dP)
+            flagged |= {(int(c), a, int(k)) for c, k in zip(*np.nonzero(sing))}
+        return n_new, dPcol, flagged
 
     def step(self, prob, G, n_prev, n_old, dt, active=None, in_memory=False, work_stride=1):
         """every atom of every column -> (n_new, DPOPS_COL, {(col, atom, depth)} flagged)"""

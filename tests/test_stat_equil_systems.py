@@ -1,8 +1,10 @@
 """The statistical-equilibrium solve, system by system, at every size (tests/se_cases.py): on the oracle here, on the HIP library
-under -m gpu -- the register instances k_stat_equil_reg<2..8>, the LDS kernel from 9 to 16 levels, the refusal at 17."""
+under -m gpu -- the register instances k_stat_equil_reg<2..8>, the LDS kernel from 9 to 16 levels, the refusal at 17 -- and, here
+again, the device's own solve (lsx_solve_dev.h) compiled for the CPU on the oracle's Gamma."""
 import pytest
 
 import se_cases
+import td_cases
 from se_cases import NLS
 
 FAMILIES = sorted(se_cases.FAMILIES)
@@ -34,6 +36,24 @@ def test_oracle_names_the_system_the_reference_raises_on_first(oracle_lib):
 @pytest.mark.parametrize('Nl', [2, 5, 9])
 def test_oracle_nan_in_the_rates_is_a_singular_system(oracle_lib, Nl):
     se_cases.nan_in_the_rates(oracle_lib, Nl)
+
+
+# ---- the device's solve, compiled for the CPU ---------------------------------------------------------------------------------
+@pytest.fixture(scope='module')
+def host():
+    return td_cases.HostLib()
+
+
+@pytest.mark.parametrize('Nl', NLS)
+@pytest.mark.parametrize('name', FAMILIES)
+def test_host_family(oracle_lib, host, name, Nl):
+    """the register form up to 8 levels (the in-memory form at work strides 1 and 64 gives its bits), the in-memory form above"""
+    se_cases.host_family(oracle_lib, host, name, Nl)
+
+
+@pytest.mark.parametrize('Nl', [5, 9])
+def test_host_singular_and_nan_systems_among_regular_ones(oracle_lib, host, Nl):
+    se_cases.host_bad_systems(oracle_lib, host, Nl)
 
 
 # ---- the HIP library ---------------------------------------------------------------------------------------------------------

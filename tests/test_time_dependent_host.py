@@ -1,4 +1,4 @@
-"""The implicit rate-equation step without a GPU (include/lsx_hip_timedep.h): the formulas of lsx_timedep_dev.h compiled for the CPU
+"""The implicit rate-equation step without a GPU (include/lsx_hip_timedep.h): the solve of lsx_solve_dev.h compiled for the CPU
 (liblsx_td_host.so) on the inputs of the GPU tests -- every family, size and shape, Gamma from the oracle's formal solution --
 against the exact solve and its bars (tests/td_cases.py), which also verifies the redraw cap and the vacuity assertion before
 anything goes to a GPU; the stand-alone sanitizer program; header, binding and export; the resource report; and the checker's
