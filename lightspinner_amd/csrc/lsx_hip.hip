@@ -928,7 +928,8 @@ k_stat_equil_reg(const double* __restrict__ Gamma, const double* __restrict__ nT
         mx = (ch != ch || mx != mx) ? __builtin_nan("") : fmax(mx, ch);   // change.max(): NaN wins inside one depth
         nk[(size_t)i * Ns] = b[i];
     }
-    if (mx == mx) atomic_max_nonneg(&dPcol[col], mx);          // builtin max over depths drops NaN (rh_method.py:741)
+    // builtin max over depths drops NaN (rh_method.py:741); one atomic per run of lanes in the same column (lsx_solve_flag.h)
+    column_max(dPcol, col, mx == mx ? static_cast<unsigned long long>(__double_as_longlong(fabs(mx))) : 0ull);
 }
 
 // FETCH_SIZE calibration (profiles/calibrate.py): read `rows` x `seg` doubles exactly once in the sweep
