@@ -250,6 +250,14 @@ class LsxLibrary:
             d.lsx_hip_stokes_rays.restype = C.c_int
             d.lsx_hip_stokes_rays_work_cap.argtypes = [C.c_void_p, C.c_size_t]
             d.lsx_hip_stokes_rays_work_cap.restype = C.c_int
+        self.has_stokes_response = hasattr(d, 'lsx_hip_response_stokes')      # include/lsx_hip_stokes_response.h
+        if self.has_stokes_response:
+            ip32 = C.POINTER(C.c_int32)
+            d.lsx_hip_response_stokes.argtypes = [C.c_void_p, C.c_int32, _dp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp,
+                                                  ip32, ip32, _dp, _dp, C.c_uint32, _dp, C.c_int32, ip32, _dp, C.c_size_t, _dp, C.c_size_t]
+            d.lsx_hip_response_stokes.restype = C.c_int
+            d.lsx_hip_response_stokes_work_cap.argtypes = [C.c_void_p, C.c_size_t]
+            d.lsx_hip_response_stokes_work_cap.restype = C.c_int
         self.has_background = hasattr(d, 'lsx_hip_background')         # include/lsx_hip_background.h
         if self.has_background:
             ip32 = C.POINTER(C.c_int32)

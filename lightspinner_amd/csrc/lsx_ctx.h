@@ -157,6 +157,12 @@ struct lsx_ctx : lsxd::LsxPlan {        // the plan (lsx_plan.h: dimensions, tab
     size_t stokes_tab_bytes = 0;
     double* d_stokes_work = nullptr;
     size_t stokes_work_doubles = 0, stokes_work_cap = 0;    // cap 0: the default of include/lsx_hip_stokes.h
+    // ... and of lsx_hip_response_stokes (lsx_stokes_response.hip): pattern tables and requested depths of a call, and the arrays of
+    // a pass (angles, field, nodes, kept states, the two results)
+    char* d_stresp_tab = nullptr;
+    size_t stresp_tab_bytes = 0;
+    double* d_stresp_work = nullptr;
+    size_t stresp_work_doubles = 0, stresp_work_cap = 0;    // cap 0: the default of include/lsx_hip_stokes_response.h
     // Ng acceleration of the populations (lsx_ng.hip, include/lsx_hip_ng.h): off (order 0) unless lsx_hip_ng_configure turns it on
     int ng_order = 0, ng_delay = 0;
     double* d_ng_hist = nullptr;         // [col][order + 2][NLtot][k]: the stored populations, slot = the column's counter

@@ -1,11 +1,13 @@
 // lsx_stokes_dev.h -- the formulas of the polarised final pass (include/lsx_hip_stokes.h) as functions that a host
-// compiler also accepts: lsx_stokes.hip runs them on the device, lsx_stokes_host.cpp on the CPU for the tests.
+// compiler also accepts: lsx_stokes.hip and lsx_stokes_response.hip run them on the device, lsx_stokes_host.cpp on the CPU for the tests.
 //
 //   faraday_voigt     w(v + i a) = H + i F: the trapezoid sum and pole term of dev_voigt (lsx_voigt.h) with the imaginary parts kept
 //   geometry          the field's direction cosines against a ray and its sky-plane basis
 //   line_profiles     phi_q, psi_q, q = -1, 0, +1: the sums over a line's Zeeman components
 //   line_add          a line's share of the propagation matrix and the emission vector (Landi Degl'Innocenti & Landolfi 2004, 9.32)
 //   delo_step         one step of the DELO-linear rule (Rees, Murphy & Durrant 1989) with the 4 x 4 solve in registers
+//   response_walk     the two walks of the response functions to the field (lsx_stokes_response.hip): up over stored nodes keeping the
+//                     ray's state, down with the 4 x 4 transfer matrix (transfer_step) and the replay of the steps a depth's node enters
 // Nothing here comes from the reference, which has no polarised formal solution.
 #pragma once
 #include <cmath>
@@ -240,6 +242,197 @@ LSXST_HD void delo_step(Ray& r, const Acc& a, double adz_zmu, const W2F& wf, boo
         n.I += r.I * (w0 - w0p) + (w0p * r.SI - w0 * n.SI) + (w1p - w1) * dS;
     }
     r = n;
+}
+
+// ---- response functions of the emergent Stokes vector to the field at one depth (include/lsx_hip_stokes_response.h) ----
+// A NODE is what the solver needs of a depth, 11 doubles.  It is kept as the depth's Acc (eta, rho, eps), not as what ray_set makes of
+// it (eta_I, K', S'): every step of a walk over nodes is then delo_step itself, ray_set included -- one text, and on the host build
+// (no contraction) the walk up has the bits of the walk of lsx_stokes_host.cpp.  The division by eta_I is redone per step.
+// Stage 1 stores the node of every depth for every field VARIANT: 0 the call's field, 1 + 2 i + s the i-th requested parameter moved
+// by +a/2 (s = 0) or -a/2 (s = 1) AT THAT DEPTH.  Stage 2 (response_walk) never forms a profile.
+constexpr int kNodeDoubles = 11;
+constexpr int kStateDoubles = 5;       // the ray's I, Q, U, V and dt after the step into a depth
+
+// the field of a variant: par 0 B, 1 gammaB, 2 chiB; up: +a/2, else -a/2 (p + a/2 and p - a/2 as a caller forms them)
+LSXST_HD void field_variant(int par, bool up, double amp, double& B, double& g, double& x)
+{
+    const double h = 0.5 * amp;
+    double& t = par == 0 ? B : (par == 1 ? g : x);
+    t = up ? t + h : t - h;
+}
+
+// node <-> 11 doubles `stride` apart (the wavelength runs fastest in the stores: stride = the window's length)
+template <class P>
+LSXST_HD void node_store(const Acc& a, P dst, size_t stride)
+{
+    dst[0] = a.eI; dst[stride] = a.eQ; dst[2 * stride] = a.eU; dst[3 * stride] = a.eV;
+    dst[4 * stride] = a.rQ; dst[5 * stride] = a.rU; dst[6 * stride] = a.rV;
+    dst[7 * stride] = a.mI; dst[8 * stride] = a.mQ; dst[9 * stride] = a.mU; dst[10 * stride] = a.mV;
+}
+template <class P>
+LSXST_HD void node_load(Acc& a, P src, size_t stride)
+{
+    a.eI = src[0]; a.eQ = src[stride]; a.eU = src[2 * stride]; a.eV = src[3 * stride];
+    a.rQ = src[4 * stride]; a.rU = src[5 * stride]; a.rV = src[6 * stride];
+    a.mI = src[7 * stride]; a.mQ = src[8 * stride]; a.mU = src[9 * stride]; a.mV = src[10 * stride];
+}
+
+// The emergent vector is affine in the vector at depth m: S_0 = T_m S_m + c_m under the call's own nodes.  T <- T M, M the linear
+// part of the DELO step from the depth behind (u) into this one (n):  M = A^-1 (E - G K'_u), A = 1 + (F - G) K'_n as in delo_step,
+// plus, at the end point, r.I (w0 - w0p) in the I row (dt_prev: the optical thickness of the interval behind u).
+// Row by row: y A = t  <=>  A^T y^T = t^T (A^T: A with the rho' block's signs turned, the same pivots' argument), then y (E - G K'_u).
+template <class W2F>
+LSXST_HD void transfer_step(double (&T)[4][4], const Acc& au, const Acc& an, double adz_zmu, const W2F& wf, bool last, double dt_prev)
+{
+    Ray u, n;
+    ray_set(u, au);
+    ray_set(n, an);
+    const double dtau = 0.5 * (u.eI + n.eI) * adz_zmu;
+    double w0, w1;
+    wf(dtau, w0, w1);
+    const double E = 1.0 - w0, G = w1 / dtau, Fa = w0 - G;
+    double ends = 0.0;
+    if (last) {
+        double w0p, w1p;
+        wf(dt_prev, w0p, w1p);
+        ends = w0 - w0p;
+    }
+    double A[4][4] = {{1.0, Fa * n.q, Fa * n.u, Fa * n.v},
+                      {Fa * n.q, 1.0, -(Fa * n.rv), Fa * n.ru},
+                      {Fa * n.u, Fa * n.rv, 1.0, -(Fa * n.rq)},
+                      {Fa * n.v, -(Fa * n.ru), Fa * n.rq, 1.0}};
+    double b[4][4];                    // b[.][i]: the i-th row of T as a right-hand side
+    LSXST_UNROLL
+    for (int i = 0; i < 4; ++i) {
+        LSXST_UNROLL
+        for (int j = 0; j < 4; ++j) b[j][i] = T[i][j];
+    }
+    LSXST_UNROLL
+    for (int k = 0; k < 3; ++k) {
+        const double rp = 1.0 / A[k][k];
+        LSXST_UNROLL
+        for (int i = k + 1; i < 4; ++i) {
+            const double f = A[i][k] * rp;
+            LSXST_UNROLL
+            for (int j = k + 1; j < 4; ++j) A[i][j] -= f * A[k][j];
+            LSXST_UNROLL
+            for (int c = 0; c < 4; ++c) b[i][c] -= f * b[k][c];
+        }
+    }
+    LSXST_UNROLL
+    for (int c = 0; c < 4; ++c) {
+        const double y3 = b[3][c] / A[3][3];
+        const double y2 = (b[2][c] - A[2][3] * y3) / A[2][2];
+        const double y1 = (b[1][c] - A[1][2] * y2 - A[1][3] * y3) / A[1][1];
+        const double y0 = b[0][c] - A[0][1] * y1 - A[0][2] * y2 - A[0][3] * y3;
+        const double t0 = T[c][0];
+        T[c][0] = E * y0 - G * (y1 * u.q + y2 * u.u + y3 * u.v) + t0 * ends;
+        T[c][1] = E * y1 - G * (y0 * u.q - y2 * u.rv + y3 * u.ru);
+        T[c][2] = E * y2 - G * (y0 * u.u + y1 * u.rv - y3 * u.rq);
+        T[c][3] = E * y3 - G * (y0 * u.v - y1 * u.ru + y2 * u.rq);
+    }
+}
+
+// What a walk needs of its surroundings, as small function objects so that the device and the host run this text:
+//   z(k)                      the height of depth k
+//   nodes(a, var, k)          the node of depth k under variant var -> the Acc a
+//   state.put(k, r)           keep r's I, Q, U, V, dt (the ray after the step into k);  state.get(k, r) the reverse
+//   out(i, jk, d[4])          the response to the i-th requested parameter at the jk-th requested depth
+// The steps the node of depth j enters, and so what is replayed with the node of a variant in j's place:
+//   the step into j and the step into j - 1 (as the depth behind);
+//   j >= Ns - 2: the thermalised start value, which reads eta_I of the two lowest depths -- the replay starts at the beginning (it
+//   does so under a ZERO lower boundary too: the start is then 0 either way);
+//   j <= 2: the end point's I reads dt of the interval behind it, dtau(2, 1), as well as its own -- the replay runs to the surface
+//   and no T is applied.
+// Otherwise the replay starts from the kept state of depth j + 1 and ends at m = j - 1, and the response is T_m (S_m^+ - S_m^-) / a.
+template <class ZAt, class Nodes, class W2F>
+struct ResponseRay {
+    int Ns;
+    double zmu;
+    bool thermal;
+    double Be, Bn;
+    const ZAt& z;
+    const Nodes& nodes;
+    const W2F& wf;
+
+    LSXST_HD void step(Ray& ray, int var, int k) const
+    {
+        Acc a;
+        nodes(a, var, k);
+        const double adz = fabs(z(k + 1) - z(k));
+        if (k == Ns - 2 && thermal) ray.I = thermal_start(Be, Bn, adz * zmu, ray.eI, a.eI);
+        delo_step(ray, a, adz * zmu, wf, k == 0);
+    }
+};
+
+template <class ZAt, class Nodes, class State, class W2F, class Out>
+LSXST_HD void response_walk(int Ns, const ZAt& z, double zmu, bool thermal, double Be, double Bn, const W2F& wf, const Nodes& nodes,
+                            const State& state, int npar, const double* amp, int nk, const int32_t* ks, const Out& out, double (&S)[4])
+{
+    const ResponseRay<ZAt, Nodes, W2F> rr{Ns, zmu, thermal, Be, Bn, z, nodes, wf};
+    // ---- up: the walk of the Stokes pass over the stored nodes of the call's own field ----
+    Ray ray;
+    Acc a0;
+    ray_init(ray);
+    nodes(a0, 0, Ns - 1);
+    ray_set(ray, a0);
+    for (int k = Ns - 2; k >= 0; --k) {
+        rr.step(ray, 0, k);
+        state.put(k, ray);
+    }
+    S[0] = ray.I; S[1] = ray.Q; S[2] = ray.U; S[3] = ray.V;
+    // ---- down from the surface ----
+    double T[4][4];
+    LSXST_UNROLL
+    for (int i = 0; i < 4; ++i) {
+        LSXST_UNROLL
+        for (int j = 0; j < 4; ++j) T[i][j] = i == j ? 1.0 : 0.0;
+    }
+    int m = 0;
+    for (int jk = 0; jk < nk; ++jk) {
+        const int j = ks ? ks[jk] : jk;
+        const int k_end = j <= 2 ? 0 : j - 1;
+        for (; m < k_end; ++m) {
+            Acc u, n;
+            nodes(u, 0, m + 1);
+            nodes(n, 0, m);
+            double dtp = 1.0;
+            if (m == 0) {
+                Ray s1;
+                state.get(1, s1);
+                dtp = s1.dt;
+            }
+            transfer_step(T, u, n, fabs(z(m + 1) - z(m)) * zmu, wf, m == 0, dtp);
+        }
+        for (int i = 0; i < npar; ++i) {
+            double d[4] = {0.0, 0.0, 0.0, 0.0};
+            for (int sg = 0; sg < 2; ++sg) {
+                const int var = 1 + 2 * i + sg;
+                Ray r;
+                Acc a;
+                ray_init(r);
+                int k;
+                if (j >= Ns - 2) {
+                    nodes(a, j == Ns - 1 ? var : 0, Ns - 1);
+                    ray_set(r, a);
+                    k = Ns - 2;
+                } else {
+                    nodes(a, 0, j + 1);
+                    ray_set(r, a);
+                    state.get(j + 1, r);
+                    k = j;
+                }
+                for (; k >= k_end; --k) rr.step(r, k == j ? var : 0, k);
+                if (sg == 0) { d[0] = r.I; d[1] = r.Q; d[2] = r.U; d[3] = r.V; }
+                else { d[0] -= r.I; d[1] -= r.Q; d[2] -= r.U; d[3] -= r.V; }
+            }
+            double o[4];
+            LSXST_UNROLL
+            for (int c = 0; c < 4; ++c)
+                o[c] = (k_end == 0 ? d[c] : T[c][0] * d[0] + T[c][1] * d[1] + T[c][2] * d[2] + T[c][3] * d[3]) / amp[i];
+            out(i, jk, o);
+        }
+    }
 }
 
 } // namespace lsxst

@@ -93,6 +93,37 @@ void walk(int Ns, const double* z, double mu, bool thermal, double Be, double Bn
     out[0] = ray.I; out[1] = ray.Q; out[2] = ray.U; out[3] = ray.V;
 }
 
+// the lines handed over to lsx_stokes_host_window / lsx_stokes_host_response and what a point of a ray makes of them: eta, rho, eps
+// of wavelength q at depth k with the field (Bk, gk, xk) there
+struct WindowLines {
+    int Ns, nla, nlines;
+    const double *wav, *chi_c, *eta_c, *lambda0, *nd, *ne, *aD, *vB, *vlos;
+    const uint8_t* active;
+    const int32_t* line;
+    const double *tab, *W;
+
+    Acc at(int q, int k, double Bk, double gk, double xk, double mu) const
+    {
+        const double w = wav[q];
+        Acc a;
+        acc_init(a, chi_c[(size_t)q * Ns + k], eta_c[(size_t)q * Ns + k]);
+        const Geo g = geometry(gk, xk, mu);
+        for (int l = 0; l < nlines; ++l) {
+            if (!active[(size_t)l * nla + q]) continue;
+            const size_t x = (size_t)l * Ns + k;
+            const int nc = line[2 * l];
+            const double vb = vB[x], l0 = lambda0[l];
+            const double v = (w - l0) * kCLight / (vb * l0);
+            const double rn = 1.0 / (std::sqrt(M_PI) * vb);
+            const double vZ = nc > 0 ? kLarmor * (kNM_TO_M * l0) * Bk / vb : 0.0;
+            const Prof pr = line_profiles(nc, tab + kCompDoubles * line[2 * l + 1], aD[x], v + 1.0 * (mu * vlos[k] / vb), vZ, W);
+            if (nc > 0) line_add(a, nd[x], ne[x], pr, rn, g);
+            else line_add_plain(a, nd[x], ne[x], pr, rn);
+        }
+        return a;
+    }
+};
+
 } // namespace
 
 extern "C" {
@@ -194,30 +225,85 @@ int lsx_stokes_host_window(int32_t Ns, int32_t nla, const double* z, const doubl
     std::vector<double> tab;
     if ((rc = pack_patterns(nlines, ncomp, alpha, strength, shift, wanted, line, tab, msg))) return rc;
     tab.resize(tab.size() + kCompDoubles, 0.0);
-    const double* W = voigt_table();
+    const WindowLines wl{Ns, nla, nlines, wav, chi_c, eta_c, lambda0, nd, ne, aD, vB, vlos, active, line.data(), tab.data(), voigt_table()};
     for (int q = 0; q < nla; ++q) {
         const double w = wav[q];
-        auto acc_at = [&](int k) {
-            Acc a;
-            acc_init(a, chi_c[(size_t)q * Ns + k], eta_c[(size_t)q * Ns + k]);
-            const Geo g = geometry(gammaB[k], chiB[k], mu);
-            for (int l = 0; l < nlines; ++l) {
-                if (!active[(size_t)l * nla + q]) continue;
-                const size_t x = (size_t)l * Ns + k;
-                const int nc = line[2 * l];
-                const double vb = vB[x], l0 = lambda0[l];
-                const double v = (w - l0) * kCLight / (vb * l0);
-                const double rn = 1.0 / (std::sqrt(M_PI) * vb);
-                const double vZ = nc > 0 ? kLarmor * (kNM_TO_M * l0) * B[k] / vb : 0.0;
-                const Prof pr = line_profiles(nc, tab.data() + kCompDoubles * line[2 * l + 1], aD[x], v + 1.0 * (mu * vlos[k] / vb), vZ, W);
-                if (nc > 0) line_add(a, nd[x], ne[x], pr, rn, g);
-                else line_add_plain(a, nd[x], ne[x], pr, rn);
-            }
-            return a;
-        };
+        auto acc_at = [&](int k) { return wl.at(q, k, B[k], gammaB[k], chiB[k], mu); };
         double o[4];
         walk(Ns, z, mu, !lower_zero, planck(temperature[Ns - 1], w), planck(temperature[Ns - 2], w), ulp, endpoint != 0, acc_at, o);
         for (int s = 0; s < 4; ++s) out[(size_t)s * nla + q] = o[s];
+    }
+    return LSX_OK;
+}
+
+// What lsx_hip_response_stokes computes for one column, one angle and a window (include/lsx_hip_stokes_response.h), by its two
+// stages through the same header functions: the nodes of every depth under every field variant (node_store), then response_walk.
+// Arguments as lsx_stokes_host_window (the end point as the kernel has it), then params, amplitude[3], nk, ks (null: all depths).
+// -> rf [npar][4][nla][nk], stokes [4][nla] (may be null).  Returns the code of the entry's rules for field, patterns and these.
+int lsx_stokes_host_response(int32_t Ns, int32_t nla, const double* z, const double* temperature, const double* wav, const double* chi_c,
+                             const double* eta_c, int32_t nlines, const double* lambda0, const double* nd, const double* ne,
+                             const double* aD, const double* vB, const uint8_t* active, const int32_t* ncomp, const int32_t* alpha,
+                             const double* strength, const double* shift, const double* vlos, const double* B, const double* gammaB,
+                             const double* chiB, double mu, int32_t lower_zero, int32_t ulp, uint32_t params, const double* amplitude,
+                             int32_t nk, const int32_t* ks, double* rf, double* stokes)
+{
+    if (Ns < 3 || nla < 1 || !(mu > 0.0 && mu <= 1.0) || !rf) return LSX_EINVAL;
+    std::string msg;
+    int rc = check_field((size_t)Ns, B, gammaB, chiB, msg);
+    if (!rc) rc = check_patterns(nlines, ncomp, alpha, strength, shift, msg);
+    if (!rc) rc = check_response(params, amplitude, Ns, nk, ks, 1, 0, B, msg);
+    if (rc) return rc;
+    std::vector<uint8_t> wanted((size_t)(nlines > 0 ? nlines : 1), 1);
+    std::vector<int32_t> line;
+    std::vector<double> tab;
+    if ((rc = pack_patterns(nlines, ncomp, alpha, strength, shift, wanted, line, tab, msg))) return rc;
+    tab.resize(tab.size() + kCompDoubles, 0.0);
+    int par[3] = {0, 0, 0};
+    const int npar = response_params(params, par);
+    const int nvar = 1 + 2 * npar, nkk = ks ? nk : Ns;
+    double amp[3] = {0.0, 0.0, 0.0};
+    for (int i = 0; i < npar; ++i) amp[i] = amplitude[par[i]];
+    std::vector<uint8_t> kreq((size_t)Ns, ks ? 0 : 1);
+    for (int i = 0; i < nkk && ks; ++i) kreq[ks[i]] = 1;
+    const WindowLines wl{Ns, nla, nlines, wav, chi_c, eta_c, lambda0, nd, ne, aD, vB, vlos, active, line.data(), tab.data(), voigt_table()};
+    // ---- stage 1: [nvar][Ns][11][nla]; a variant's node is formed (and read) at requested depths only ----
+    const size_t S = (size_t)nla;
+    std::vector<double> nodes((size_t)nvar * Ns * kNodeDoubles * S, NAN), state((size_t)Ns * kStateDoubles * S, NAN);
+    for (int k = 0; k < Ns; ++k)
+        for (int var = 0; var < nvar; ++var) {
+            if (var > 0 && !kreq[k]) continue;
+            double Bk = B[k], gk = gammaB[k], xk = chiB[k];
+            if (var > 0) field_variant(par[(var - 1) >> 1], ((var - 1) & 1) == 0, amp[(var - 1) >> 1], Bk, gk, xk);
+            for (int q = 0; q < nla; ++q)
+                node_store(wl.at(q, k, Bk, gk, xk, mu), nodes.data() + ((size_t)var * Ns + k) * kNodeDoubles * S + q, S);
+        }
+    // ---- stage 2 ----
+    const W2Host wf{ulp};
+    for (int q = 0; q < nla; ++q) {
+        const auto zat = [&](int k) { return z[k]; };
+        const auto nod = [&](Acc& n, int var, int k) { node_load(n, nodes.data() + ((size_t)var * Ns + k) * kNodeDoubles * S + q, S); };
+        struct StateHost {
+            double* base;
+            size_t S;
+            void put(int k, const Ray& r) const
+            {
+                double* s = base + (size_t)k * kStateDoubles * S;
+                s[0] = r.I; s[S] = r.Q; s[2 * S] = r.U; s[3 * S] = r.V; s[4 * S] = r.dt;
+            }
+            void get(int k, Ray& r) const
+            {
+                const double* s = base + (size_t)k * kStateDoubles * S;
+                r.I = s[0]; r.Q = s[S]; r.U = s[2 * S]; r.V = s[3 * S]; r.dt = s[4 * S];
+            }
+        };
+        const StateHost st{state.data() + q, S};
+        const auto out = [&](int i, int jk, const double (&o)[4]) {
+            for (int c = 0; c < 4; ++c) rf[(((size_t)i * 4 + c) * nla + q) * nkk + jk] = o[c];
+        };
+        double Sv[4];
+        response_walk(Ns, zat, 1.0 / mu, !lower_zero, planck(temperature[Ns - 1], wav[q]), planck(temperature[Ns - 2], wav[q]), wf, nod, st,
+                      npar, amp, nkk, ks, out, Sv);
+        for (int c = 0; c < 4 && stokes; ++c) stokes[(size_t)c * nla + q] = Sv[c];
     }
     return LSX_OK;
 }

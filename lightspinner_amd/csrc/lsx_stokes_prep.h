@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/lsx_hip_stokes.h"
+#include "../../include/lsx_hip_stokes_response.h"
 #include "lsx_stokes_dev.h"
 
 namespace lsxst {
@@ -102,6 +103,60 @@ inline int pack_patterns(int nlines, const int32_t* ncomp, const int32_t* alpha,
                                   "narrow the window", tab.size() / kCompDoubles, LSX_STOKES_MAX_WINDOW_COMPONENTS);
         msg = buf;
         return LSX_EUNSUPPORTED;
+    }
+    return LSX_OK;
+}
+
+// ---- the rules lsx_hip_response_stokes adds (include/lsx_hip_stokes_response.h) ----
+// the requested parameters in the order B, gammaB, chiB -> par[npar] (0, 1, 2); returns npar
+inline int response_params(uint32_t params, int par[3])
+{
+    int n = 0;
+    for (int b = 0; b < 3; ++b)
+        if (params & (1u << b)) par[n++] = b;
+    return n;
+}
+
+// params, amplitude[3], the depths (ks null: all Ns, nk is not looked at) and, where B is requested, B >= a_B / 2 at every requested
+// depth of the ncol columns of B [ncol][Ns] (col0: the first one's number, for the message).  -> LSX_OK or LSX_EINVAL with a message
+inline int check_response(uint32_t params, const double* amplitude, int Ns, int32_t nk, const int32_t* ks, size_t ncol, int col0,
+                          const double* B, std::string& msg)
+{
+    static const char* const name[3] = {"B", "gammaB", "chiB"};
+    char buf[200];
+    if (params == 0 || (params & ~7u)) {
+        snprintf(buf, sizeof buf, "params = 0x%x: need at least one of the bits B (1), gammaB (2), chiB (4) and no other", (unsigned)params);
+        msg = buf;
+        return LSX_EINVAL;
+    }
+    if (!amplitude) { msg = "null amplitude"; return LSX_EINVAL; }
+    for (int b = 0; b < 3; ++b)
+        if ((params & (1u << b)) && !(std::isfinite(amplitude[b]) && amplitude[b] > 0.0)) {
+            snprintf(buf, sizeof buf, "the amplitude of %s is %g: it must be finite and positive", name[b], amplitude[b]);
+            msg = buf;
+            return LSX_EINVAL;
+        }
+    if (ks) {
+        if (nk < 1) { snprintf(buf, sizeof buf, "nk = %d, need at least one depth", (int)nk); msg = buf; return LSX_EINVAL; }
+        for (int i = 0; i < nk; ++i)
+            if (ks[i] < 0 || ks[i] >= Ns || (i && ks[i] <= ks[i - 1])) {
+                snprintf(buf, sizeof buf, "ks[%d] = %d: the depths must increase strictly inside [0, %d)", i, (int)ks[i], Ns);
+                msg = buf;
+                return LSX_EINVAL;
+            }
+    }
+    if (params & 1u) {
+        const int n = ks ? nk : Ns;
+        for (size_t c = 0; c < ncol; ++c)
+            for (int i = 0; i < n; ++i) {
+                const int k = ks ? ks[i] : i;
+                if (B[c * Ns + k] < 0.5 * amplitude[0]) {
+                    snprintf(buf, sizeof buf, "column %d, depth %d: B = %g is below half the amplitude %g: the changed field would be "
+                                              "negative (leave field-free depths out with ks)", col0 + (int)c, k, B[c * Ns + k], amplitude[0]);
+                    msg = buf;
+                    return LSX_EINVAL;
+                }
+            }
     }
     return LSX_OK;
 }

@@ -1,0 +1,377 @@
+// lsx_stokes_response.hip -- response functions of the emergent Stokes vector to the field strength, inclination and azimuth at every
+// depth (include/lsx_hip_stokes_response.h, lsx_hip_response_stokes).  Read-only on the context; gfx950 only.
+//
+// In the field-free method the response to the field at one depth is the change of one polarised formal solution.  The absorption
+// matrix of a depth depends on the field at that depth only and the DELO-linear recursion is affine in the Stokes vector, so two
+// stages do for all depths what 6 Nspace + 1 runs of k_stokes_rays (lsx_stokes.hip) would:
+//   k_response_nodes   one wavefront = 64 wavelengths of the window of one column at ONE depth under ONE field variant (the call's
+//                      field, or one parameter moved by +-a/2 at that depth): the depth's eta, rho, eps by the text of k_stokes_rays
+//                      (final_column, line_profiles, line_add, line_add_plain, the LDS tables), stored as the depth's NODE (lsx_stokes_dev.h:
+//                      the 11 doubles the solver needs of it) with the wavelength running fastest.  No ray state: depths and variants
+//                      are the grid's z.
+//                      The variants of gammaB and chiB repeat the profiles of the call's field (only `geometry` differs): that is NOT
+//                      exploited.  A rolled loop over the variants of a depth that kept the profiles would have to keep them per line
+//                      while several lines add into one Acc, i.e. carry five Accs (55 doubles) beside the profile function, whose
+//                      kernel already stands at 242 vector registers with one; and sums free of the geometry would change the bits
+//                      of the unperturbed node.  So every variant is a block of its own and forms its profiles.
+//   k_response_walk    lane = wavelength, block z = angle; no profile function.  response_walk (lsx_stokes_dev.h): the walk up over
+//                      the stored nodes keeps the ray's state at every depth; the walk down carries the 4 x 4 matrix T_m and redoes,
+//                      per requested depth, parameter and sign, the steps that depth's node enters.
+// The work arrays are padded to whole wavefronts of wavelengths, so that a spare lane (it walks the window's last wavelength: the
+// exponential's table is read wave-wide) has a slot of its own: one writer per value.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "../../include/lsx_hip.h"
+#include "lsx_final_host.h"
+#include "lsx_stokes_dev.h"
+#include "lsx_stokes_prep.h"
+
+using namespace lsxd;
+
+namespace {
+
+constexpr size_t kWorkCapDefault = (size_t)256 << 20;      // bytes (include/lsx_hip_stokes_response.h)
+
+struct RespParams {
+    // ---- what k_stokes_rays reads (lsx_stokes.hip, StokesParams) ----
+    int32_t Ns, Nspect, NLtot, Natoms, NlinesA, Ncont, L, Nrays;
+    int32_t col0, nmu, mu0;     // first column of the launch; angles of the call; the angle of this launch of k_response_nodes
+    int32_t la0, nla;
+    int32_t phi_compact, sca_per_lambda, phi_G;
+    int32_t ntab;
+    int64_t til_col, phi_col, sca_col, fstride;
+    const double *wavelength, *u_la, *exp2_tab, *voigt_W, *mu;
+    const int32_t* la_ptr;
+    const FinalEnt* ents;
+    const int32_t* la_tile;
+    const double *height, *temperature, *n, *nsr, *bgchi_T, *bgeta_T, *J_T, *E_T, *sca, *phi_T;
+    const double *aDamp, *vBroad, *vlos;
+    const uint8_t* prof_kind;
+    const int32_t* bnd;
+    const int32_t* pat_line;
+    const double* pat_tab;
+    const double* field;
+    // ---- the response's own ----
+    int32_t npar, nvar, nk, nlaP;       // requested parameters, 1 + 2 npar, requested depths, nla rounded up to whole wavefronts
+    const int32_t* par;                 // [npar] the requested parameters (0 B, 1 gammaB, 2 chiB)
+    const double* amp;                  // [npar] their amplitudes
+    const int32_t* ks;                  // [nk] requested depths, or null: all
+    const int32_t* kreq;                // [Ns]: 1 where the depth is requested
+    double* nodes;                      // [launch column][nmu][nvar][Ns][11][nlaP]
+    double* state;                      // [launch column][nmu][Ns][5][nlaP]
+    double* rf;                         // [launch column][npar][4][nla][nk][nmu]
+};
+
+struct W2Dev {                  // the linear rule's weights as the other final passes form them (lsx_dev.h)
+    const lds_f64* etab;
+    __device__ __forceinline__ void operator()(double dtau, double& w0, double& w1) const { w2(dtau, w0, w1, etab); }
+};
+
+__device__ __forceinline__ size_t node_offset(const RespParams& p, size_t cl, int m, int var, int k)
+{
+    return ((((cl * p.nmu + m) * p.nvar + var) * p.Ns + k) * (size_t)lsxst::kNodeDoubles) * p.nlaP;
+}
+
+// ---- stage 1: the node of one depth under one variant of the field ----
+__global__ void __launch_bounds__(64) k_response_nodes(const RespParams p)
+{
+    const int Ns = p.Ns, L = p.L;
+    const int k = blockIdx.z / p.nvar, var = blockIdx.z - k * p.nvar;
+    if (var > 0 && !p.kreq[k]) return;                    // (block-uniform) a variant is read at requested depths only
+    extern __shared__ double smem[];                      // the Voigt function's table (56 doubles), the patterns
+    if (threadIdx.x < 56) smem[threadIdx.x] = p.voigt_W ? p.voigt_W[threadIdx.x] : 0.0;
+    for (int e = threadIdx.x; e < p.ntab; e += 64) smem[64 + e] = p.pat_tab[e];
+    __syncthreads();
+    const lds_f64* vtab = (const lds_f64*)smem;
+    const lds_f64* ptab = vtab + 64;
+
+    const int q_raw = blockIdx.x * 64 + threadIdx.x;
+    const int q = q_raw < p.nla ? q_raw : p.nla - 1;
+    const int la = p.la0 + q;
+    const size_t col = (size_t)p.col0 + blockIdx.y;
+    const FinalColumn f = final_column(p, col, la);
+    const FinalAngles fa = final_angles(p, col);
+    const double* aD_c = p.aDamp + col * (size_t)p.NlinesA * Ns;
+    const double* vB_c = p.vBroad + col * (size_t)p.Natoms * Ns;
+    const double* vL_c = p.vlos + col * Ns;
+    const double* fld = p.field + (size_t)blockIdx.y * Ns;
+    const double wav = p.wavelength[la], u_la = p.u_la[la];
+    const double mu = p.mu[p.mu0];
+
+    const double Ev = f.Eb ? f.Eb[(size_t)k * L] : 0.0;
+    const double c0 = f.bgchi[(size_t)k * L];
+    const double h0 = f.bgeta[(size_t)k * L] + f.sca[(size_t)k * f.sstr] * f.Jd[(size_t)k * L];
+    double Bk = fld[k], gk = fld[p.fstride + k], xk = fld[2 * p.fstride + k];
+    if (var > 0) lsxst::field_variant(p.par[(var - 1) >> 1], ((var - 1) & 1) == 0, p.amp[(var - 1) >> 1], Bk, gk, xk);
+    lsxst::Acc acc;
+    lsxst::acc_init(acc, c0, h0);
+    const lsxst::Geo geo = lsxst::geometry(gk, xk, mu);
+    for (int e = f.e0; e < f.e1; ++e) {
+        const FinalEnt& t = p.ents[e];
+        const double ni = f.n_col[(size_t)t.li * Ns + k], nj = f.n_col[(size_t)t.lj * Ns + k];
+        if (t.is_line) {
+            const double nd = t.a * (ni - t.g * nj);
+            const int nc = p.pat_line[2 * t.row];
+            if (nc > 0 || fa.raydep) {
+                const lds_f64* tab = ptab + lsxst::kCompDoubles * p.pat_line[2 * t.row + 1];
+                const double vb = vB_c[(size_t)t.atom * Ns + k], ad = aD_c[(size_t)t.row * Ns + k], vl = vL_c[k];
+                const double v = (wav - t.lambda0) * kCLight / (vb * t.lambda0);
+                const double rn = 1.0 / (sqrt(M_PI) * vb);
+                const double vZ = nc > 0 ? lsxst::kLarmor * (kNM_TO_M * t.lambda0) * Bk / vb : 0.0;
+                const double ne = nj * t.Uc;
+                const lsxst::Prof pr = lsxst::line_profiles(nc, tab, ad, v + 1.0 * (mu * vl / vb), vZ, vtab);
+                if (nc > 0) lsxst::line_add(acc, nd, ne, pr, rn, geo);
+                else lsxst::line_add_plain(acc, nd, ne, pr, rn);
+            } else {
+                const size_t x = p.phi_compact ? (size_t)k : ((size_t)Ns + k) * p.Nrays;
+                const double pv = p.phi_T[phi_elem(col, p.phi_G, (size_t)p.phi_col, (size_t)t.phi_base, x, t.phi_len, t.phi_l)];
+                const double c1 = nd * pv, h1 = nj * (t.Uc * pv);
+                acc.eI += c1; acc.mI += h1;
+            }
+        } else {
+            const double pv = (f.nsr_col[(size_t)t.row * Ns + k] * Ev) * t.a;
+            const double c1 = ni * t.a - nj * pv, h1 = nj * (u_la * pv);
+            acc.eI += c1; acc.mI += h1;
+        }
+    }
+    lsxst::node_store(acc, p.nodes + node_offset(p, blockIdx.y, p.mu0, var, k) + q_raw, (size_t)p.nlaP);
+}
+
+// ---- stage 2: the walks of one ray ----
+struct ZDev {
+    const double* z;
+    __device__ __forceinline__ double operator()(int k) const { return z[k]; }
+};
+struct NodesDev {
+    const double* base;         // the lane's wavelength of [nvar][Ns][11][nlaP]
+    size_t Ns, nlaP;
+    __device__ __forceinline__ void operator()(lsxst::Acc& n, int var, int k) const
+    {
+        lsxst::node_load(n, base + ((size_t)var * Ns + k) * lsxst::kNodeDoubles * nlaP, nlaP);
+    }
+};
+struct StateDev {
+    double* base;               // the lane's wavelength of [Ns][5][nlaP]
+    size_t nlaP;
+    __device__ __forceinline__ void put(int k, const lsxst::Ray& r) const
+    {
+        double* s = base + (size_t)k * lsxst::kStateDoubles * nlaP;
+        s[0] = r.I; s[nlaP] = r.Q; s[2 * nlaP] = r.U; s[3 * nlaP] = r.V; s[4 * nlaP] = r.dt;
+    }
+    __device__ __forceinline__ void get(int k, lsxst::Ray& r) const
+    {
+        const double* s = base + (size_t)k * lsxst::kStateDoubles * nlaP;
+        r.I = s[0]; r.Q = s[nlaP]; r.U = s[2 * nlaP]; r.V = s[3 * nlaP]; r.dt = s[4 * nlaP];
+    }
+};
+struct OutDev {
+    double* rf;                 // the lane's (wavelength, angle) of [npar][4][nla][nk][nmu]; null for a spare lane
+    size_t comp, nmu;           // nla nk nmu
+    __device__ __forceinline__ void operator()(int i, int jk, const double (&o)[4]) const
+    {
+        if (!rf) return;
+        double* d = rf + (size_t)i * 4 * comp + (size_t)jk * nmu;
+        d[0] = o[0]; d[comp] = o[1]; d[2 * comp] = o[2]; d[3 * comp] = o[3];
+    }
+};
+
+__global__ void __launch_bounds__(64) k_response_walk(const RespParams p)
+{
+    extern __shared__ double smem[];                  // the exponential's table
+    for (int e = threadIdx.x; e < LSX_EXP_TAB; e += 64) smem[e] = p.exp2_tab[e];
+    __syncthreads();
+    const W2Dev wf{(const lds_f64*)smem};
+
+    const int Ns = p.Ns;
+    const int q_raw = blockIdx.x * 64 + threadIdx.x;
+    const bool valid = q_raw < p.nla;
+    const int q = valid ? q_raw : p.nla - 1;
+    const int m = blockIdx.z;
+    const size_t cl = blockIdx.y, col = (size_t)p.col0 + cl;
+    const bool lower_zero = p.bnd != nullptr && boundary_kind(p.bnd, col, LSX_BND_LOWER) == 0;
+    const double wav = p.wavelength[p.la0 + q];
+    const double Be = lsxst::planck(p.temperature[col * Ns + Ns - 1], wav), Bn = lsxst::planck(p.temperature[col * Ns + Ns - 2], wav);
+    const ZDev z{p.height + col * Ns};
+    const NodesDev nodes{p.nodes + node_offset(p, cl, m, 0, 0) + q_raw, (size_t)Ns, (size_t)p.nlaP};
+    const StateDev state{p.state + ((cl * p.nmu + m) * Ns) * (size_t)lsxst::kStateDoubles * p.nlaP + q_raw, (size_t)p.nlaP};
+    const size_t comp = (size_t)p.nla * p.nk * p.nmu;
+    const OutDev out{valid ? p.rf + cl * p.npar * 4 * comp + (size_t)q * p.nk * p.nmu + m : nullptr, comp, (size_t)p.nmu};
+    double S[4];                                      // (the walk's own emergent vector is not handed out: see the entry)
+    lsxst::response_walk(Ns, z, 1.0 / p.mu[m], !lower_zero, Be, Bn, wf, nodes, state, p.npar, p.amp, p.nk, p.ks, out, S);
+}
+
+} // namespace
+
+extern "C" int lsx_hip_response_stokes_work_cap(lsx_ctx* c, size_t nbytes)
+{
+    if (!c) return fail(LSX_EINVAL, "lsx_hip_response_stokes_work_cap: null context");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (c->d_stresp_work) HIPCHK(hipFree(c->d_stresp_work));       // the next call allocates under the new cap
+    c->d_stresp_work = nullptr;
+    c->stresp_work_doubles = 0;
+    c->stresp_work_cap = nbytes;
+    return LSX_OK;
+}
+
+extern "C" int lsx_hip_response_stokes(lsx_ctx* c, int32_t nmu, const double* mu, int32_t col0, int32_t ncol, int32_t la0, int32_t nla,
+                                       const double* B, const double* gammaB, const double* chiB,
+                                       const int32_t* ncomp, const int32_t* alpha, const double* strength, const double* shift,
+                                       uint32_t params, const double amplitude[3], int32_t nk, const int32_t* ks,
+                                       double* rf, size_t rf_bytes, double* stokes, size_t stokes_bytes)
+{
+    const char* who = "lsx_hip_response_stokes";
+    // ---- everything is checked on the host before anything is launched: first what lsx_hip_stokes_rays checks, in its order ----
+    if (!c || !mu || !B || !gammaB || !chiB || !rf) return fail(LSX_EINVAL, "%s: null argument", who);
+    if (c->Nlines && !ncomp) return fail(LSX_EINVAL, "%s: null ncomp (one count per line; zeros for no pattern)", who);
+    int rc = final_check_angles(who, nmu, mu);
+    if (!rc) rc = final_check_range(c, who, col0, ncol);
+    if (rc) return rc;
+    if (nla < 1) return fail(LSX_EINVAL, "%s: nla = %d, need at least one wavelength", who, (int)nla);
+    if (la0 < 0 || (int64_t)la0 + nla > c->Nspect)
+        return fail(LSX_EINVAL, "%s: wavelengths [%d, %d) are outside the grid's %d", who, (int)la0, (int)la0 + (int)nla, c->Nspect);
+    const int Ns = c->Nspace;
+    std::string msg;
+    if ((rc = lsxst::check_field((size_t)ncol * Ns, B, gammaB, chiB, msg))) return fail(rc, "%s: %s", who, msg.c_str());
+    if ((rc = lsxst::check_patterns(c->Nlines, ncomp, alpha, strength, shift, msg))) return fail(rc, "%s: %s", who, msg.c_str());
+    if ((rc = final_check_depths(c, who))) return rc;
+    if ((rc = final_check_columns(c, who, col0, ncol, FINAL_OTHER_ANGLE))) return rc;
+    for (int q = col0; q < col0 + ncol && c->Nlines; ++q)
+        if (c->prof_kind.empty() || !c->prof_kind[q])
+            return fail(LSX_EUNSUPPORTED, "%s: the line profiles of column %d were handed over as arrays (lsx_set_columns): the library "
+                                          "cannot know them at another angle.  Build them with lsx_set_line_profiles or "
+                                          "lsx_set_atmosphere", who, q);
+    // ---- ... then the response's own rules ----
+    if ((rc = lsxst::check_response(params, amplitude, Ns, nk, ks, (size_t)ncol, col0, B, msg))) return fail(rc, "%s: %s", who, msg.c_str());
+    int par[3] = {0, 0, 0};
+    const int npar = lsxst::response_params(params, par);
+    const int nvar = 1 + 2 * npar;
+    const int nkk = ks ? nk : Ns;
+    const size_t plane = (size_t)nla * nmu, per_s = 4 * plane, per_rf = (size_t)npar * 4 * plane * nkk;
+    if (rf_bytes != (size_t)ncol * per_rf * 8) return fail(LSX_EINVAL, "%s: rf_bytes does not match [ncol][npar][4][nla][nk][nmu]", who);
+    if (stokes && stokes_bytes != (size_t)ncol * per_s * 8) return fail(LSX_EINVAL, "%s: stokes_bytes does not match [ncol][4][nla][nmu]", who);
+    if ((int64_t)Ns * nvar > 65535 || nmu > 65535)
+        return fail(LSX_EUNSUPPORTED, "%s: Nspace x (1 + 2 parameters) = %lld or nmu = %d is above a grid's 65535", who,
+                    (long long)Ns * nvar, (int)nmu);
+
+    // the patterns of the lines that are active somewhere in the window
+    std::vector<uint8_t> wanted(std::max(1, c->Nlines), 0);
+    for (int t = 0; t < c->Ntrans; ++t) {
+        if (!c->htrans[t].is_line) continue;
+        const uint8_t* act = c->active.data() + (size_t)t * c->Nspect;
+        for (int la = la0; la < la0 + nla; ++la)
+            if (act[la]) { wanted[c->trans_row[t]] = 1; break; }
+    }
+    std::vector<int32_t> pat_line;
+    std::vector<double> pat_tab;
+    if ((rc = lsxst::pack_patterns(c->Nlines, ncomp, alpha, strength, shift, wanted, pat_line, pat_tab, msg)))
+        return fail(rc, "%s: %s", who, msg.c_str());
+    HIPCHK(hipSetDevice(c->device));
+    if ((rc = final_tables(c, who))) return rc;
+
+    // the tables of the call: [pat_line | par | kreq | ks], [amp | pat_tab]
+    std::vector<int32_t> ints(pat_line);
+    const size_t o_par = ints.size();
+    ints.insert(ints.end(), par, par + 3);
+    const size_t o_kreq = ints.size();
+    ints.resize(o_kreq + Ns, ks ? 0 : 1);
+    const size_t o_ks = ints.size();
+    for (int i = 0; i < nkk && ks; ++i) {
+        ints[o_kreq + ks[i]] = 1;
+        ints.push_back(ks[i]);
+    }
+    const size_t int_bytes = (ints.size() * sizeof(int32_t) + 7) & ~(size_t)7;
+    const double amps[4] = {amplitude[par[0]], amplitude[par[npar > 1 ? 1 : 0]], amplitude[par[npar > 2 ? 2 : 0]], 0.0};
+    const size_t tab_bytes = int_bytes + (4 + std::max<size_t>(1, pat_tab.size())) * 8;
+    if (c->stresp_tab_bytes < tab_bytes) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (c->d_stresp_tab) HIPCHK(hipFree(c->d_stresp_tab));
+        c->d_stresp_tab = nullptr;
+        c->stresp_tab_bytes = 0;
+        if ((rc = dmalloc(&c->d_stresp_tab, tab_bytes))) return rc;
+        c->stresp_tab_bytes = tab_bytes;
+    }
+    HIPCHK(hipMemcpyAsync(c->d_stresp_tab, ints.data(), ints.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->d_stresp_tab + int_bytes, amps, sizeof amps, hipMemcpyHostToDevice, c->stream));
+    if (!pat_tab.empty())
+        HIPCHK(hipMemcpyAsync(c->d_stresp_tab + int_bytes + sizeof amps, pat_tab.data(), pat_tab.size() * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));                      // the host vectors may go out of scope on any return below
+
+    // columns per pass: the arrays of a pass stay under the cap (one column's need if that alone is more)
+    const size_t nblk = ((size_t)nla + 63) / 64, nlaP = nblk * 64;
+    const size_t head = ((size_t)nmu + 1) & ~(size_t)1;
+    const size_t w_nodes = (size_t)nmu * nvar * Ns * lsxst::kNodeDoubles * nlaP, w_state = (size_t)nmu * Ns * lsxst::kStateDoubles * nlaP;
+    const size_t wcol = w_nodes + w_state + per_rf + 3 * (size_t)Ns;
+    const size_t cap = c->stresp_work_cap ? c->stresp_work_cap : kWorkCapDefault;
+    const size_t chunk = std::max<size_t>(1, std::min<size_t>(std::min<size_t>(ncol, 65535), cap / (wcol * 8)));     // (and a grid's y limit)
+    const size_t need = head + chunk * wcol;
+    if (c->stresp_work_doubles < need) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (c->d_stresp_work) HIPCHK(hipFree(c->d_stresp_work));
+        c->d_stresp_work = nullptr;
+        c->stresp_work_doubles = 0;
+        if ((rc = dmalloc(&c->d_stresp_work, need))) return rc;
+        c->stresp_work_doubles = need;
+    }
+    double* d_mu = c->d_stresp_work;
+    double* d_field = d_mu + head;
+    double* d_nodes = d_field + chunk * 3 * (size_t)Ns;
+    double* d_state = d_nodes + chunk * w_nodes;
+    double* d_rf = d_state + chunk * w_state;
+    HIPCHK(hipMemcpyAsync(d_mu, mu, (size_t)nmu * 8, hipMemcpyHostToDevice, c->stream));
+
+    RespParams p{};
+    p.Ns = Ns; p.Nspect = c->Nspect; p.NLtot = c->NLtot; p.Natoms = c->Natoms; p.NlinesA = std::max(1, c->Nlines);
+    p.Ncont = c->Ncont; p.L = c->L; p.Nrays = c->Nrays; p.nmu = nmu; p.la0 = la0; p.nla = nla;
+    p.phi_compact = c->phi_compact; p.sca_per_lambda = c->sca_per_lambda; p.phi_G = c->phi_group;
+    p.ntab = (int32_t)pat_tab.size();
+    p.til_col = (int64_t)c->til_col; p.phi_col = (int64_t)c->phi_col; p.sca_col = (int64_t)c->sca_col;
+    p.wavelength = c->d_wavelength; p.u_la = c->d_u_la; p.exp2_tab = c->d_exp2_tab; p.voigt_W = c->d_voigt_w; p.mu = d_mu;
+    p.la_ptr = c->d_final_ptr; p.ents = c->d_final_ent; p.la_tile = c->d_final_tile;
+    p.height = c->d_height; p.temperature = c->d_temperature; p.n = c->d_n; p.nsr = c->d_nsr;
+    p.bnd = c->d_bnd;
+    p.bgchi_T = c->d_bgchi; p.bgeta_T = c->d_bgeta; p.J_T = c->d_J[c->jcur];      // what lsx_get(LSX_J) returns at this moment
+    p.E_T = c->d_E; p.sca = c->d_sca; p.phi_T = c->d_phi;
+    p.aDamp = c->d_aDamp; p.vBroad = c->d_vBroad; p.vlos = c->d_vlos; p.prof_kind = c->d_prof_kind;
+    const int32_t* d_ints = (const int32_t*)c->d_stresp_tab;
+    p.pat_line = d_ints;
+    p.kreq = d_ints + o_kreq;
+    p.ks = ks ? d_ints + o_ks : nullptr;
+    p.par = d_ints + o_par;
+    p.amp = (const double*)(c->d_stresp_tab + int_bytes);
+    p.pat_tab = p.amp + 4;
+    p.field = d_field;
+    p.npar = npar; p.nvar = nvar; p.nk = nkk; p.nlaP = (int32_t)nlaP;
+    p.nodes = d_nodes; p.state = d_state; p.rf = d_rf;
+    const size_t lds_nodes = ((size_t)64 + pat_tab.size() + lsxst::kCompDoubles) * 8;
+    const size_t lds_walk = (size_t)LSX_EXP_TAB * 8;
+
+    for (size_t b0 = 0; b0 < (size_t)ncol; b0 += chunk) {
+        const size_t nb = std::min(chunk, (size_t)ncol - b0);
+        p.col0 = (int32_t)(col0 + b0);
+        p.fstride = (int64_t)(nb * Ns);
+        const double* const src[3] = {B, gammaB, chiB};
+        for (int a = 0; a < 3; ++a)
+            HIPCHK(hipMemcpyAsync(d_field + (size_t)a * nb * Ns, src[a] + b0 * Ns, nb * Ns * 8, hipMemcpyHostToDevice, c->stream));
+        // one launch of the nodes per angle (the profile function is evaluated per angle, as in lsx_stokes.hip), one of the walks for all
+        for (int m0 = 0; m0 < nmu; ++m0) {
+            p.mu0 = m0;
+            hipLaunchKernelGGL(k_response_nodes, dim3((unsigned)nblk, (unsigned)nb, (unsigned)(Ns * nvar)), dim3(64), lds_nodes, c->stream, p);
+        }
+        p.mu0 = 0;
+        hipLaunchKernelGGL(k_response_walk, dim3((unsigned)nblk, (unsigned)nb, (unsigned)nmu), dim3(64), lds_walk, c->stream, p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(rf + b0 * per_rf, d_rf, nb * per_rf * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));       // the arrays are re-used by the next pass
+    }
+    // The vector of the call's own field comes from the Stokes pass itself, so that it has that pass's bits by construction.  The
+    // walk up forms the same vector through the same functions (the host build's is bit for bit lsx_stokes_host_window's), but in
+    // another kernel the device compiler contracts products and sums into fused operations differently: measured on an MI355X, a
+    // quarter of the entries differ from k_stokes_rays' in the last bits (at most 1.2e-14 of I).  One more launch per angle
+    if (stokes) return lsx_hip_stokes_rays(c, nmu, mu, col0, ncol, la0, nla, B, gammaB, chiB, ncomp, alpha, strength, shift, stokes, stokes_bytes);
+    return LSX_OK;
+}

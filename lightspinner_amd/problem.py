@@ -260,6 +260,19 @@ class StokesRays:
         self.I, self.Q, self.U, self.V = I, Q, U, V
 
 
+class StokesResponse:
+    """What Engine.stokes_response returns: .rf, a dict from the names of the requested parameters ('B', 'gammaB', 'chiB') to
+    [ncol][4][nla][nk][nmu] arrays (the responses of I, Q, U, V to that parameter at the depths .ks, per tesla resp. per radian),
+    .stokes, the StokesRays of the call's own field, and .ks, .mus, .la0, .amplitudes (a dict like .rf).
+    Context.compute_stokes_response drops the column axis (and the angle axis for a scalar mu).
+    Definitions: include/lsx_hip_stokes_response.h."""
+    PARAMETERS = ('B', 'gammaB', 'chiB')
+    DEFAULT_AMPLITUDES = {'B': 1e-3, 'gammaB': 1e-3, 'chiB': 1e-3}          # T, rad, rad
+
+    def __init__(self, rf, stokes, ks, mus, la0, amplitudes):
+        self.rf, self.stokes, self.ks, self.mus, self.la0, self.amplitudes = rf, stokes, ks, mus, int(la0), amplitudes
+
+
 class NgOptions:
     """Ng acceleration of the MALI loop (include/lsx_hip_ng.h): order 1 or 2 (0: off), delay >= 0 statistical equilibria that pass
     before the first population vector is stored.  What Context(ng=...) and run_response_function(ng=...) take."""
@@ -675,6 +688,47 @@ class Engine:
                                                         _ptr(fld[1]), _ptr(fld[2]), ip(ncomp), ip(alpha), _ptr(strength), _ptr(shift),
                                                         _ptr(out), out.nbytes))
         return StokesRays(mu, la0, out[:, 0], out[:, 1], out[:, 2], out[:, 3])
+
+    def stokes_response(self, mus, B, gammaB, chiB, patterns=None, la0=0, nla=None, col0=0, ncol=None,
+                        parameters=StokesResponse.PARAMETERS, amplitudes=None, ks=None, work_cap_bytes=None):
+        """Response functions of the emergent Stokes vector to the field strength, inclination and azimuth at every depth
+        (include/lsx_hip_stokes_response.h, lsx_hip_response_stokes): RF_p[k] = (S(p_k + a_p / 2) - S(p_k - a_p / 2)) / a_p, S what
+        stokes_rays returns for the field changed at depth k of that column alone.  Arguments as stokes_rays, then
+        parameters: some of 'B', 'gammaB', 'chiB'; amplitudes: a dict from those names to a_p (None, or a name left out: 1e-3 T,
+        1e-3 rad); ks: the depths, strictly increasing (None: all).  B must be at least a_B / 2 at every requested depth where 'B'
+        is requested.  Read-only.  -> StokesResponse.  Only the HIP library computes it."""
+        from . import zeeman
+        if not getattr(self.lib, 'has_stokes_response', False):
+            raise NotImplementedError('%s (%s) does not export lsx_hip_response_stokes: polarised spectra and their response '
+                                      'functions are computed by the HIP library only' % (self.lib.path, self.lib.backend))
+        if work_cap_bytes is not None:
+            self.lib.check(self.lib.dll.lsx_hip_response_stokes_work_cap(self._h, int(work_cap_bytes)))
+        names = [parameters] if isinstance(parameters, str) else list(parameters)
+        for w in names:
+            if w not in StokesResponse.PARAMETERS:
+                raise ValueError("stokes_response: parameter %r is not one of 'B', 'gammaB', 'chiB'" % (w,))
+        names = [w for w in StokesResponse.PARAMETERS if w in names]
+        amps = dict(StokesResponse.DEFAULT_AMPLITUDES)
+        amps.update(amplitudes or {})
+        amp = f64(np.array([amps[w] for w in StokesResponse.PARAMETERS], dtype=np.float64))
+        bits = sum(1 << StokesResponse.PARAMETERS.index(w) for w in names)
+        mu = f64(np.atleast_1d(np.asarray(mus, dtype=np.float64)).reshape(-1))
+        ncol = self.ncol - int(col0) if ncol is None else int(ncol)
+        nla = self.problem.Nspect - int(la0) if nla is None else int(nla)
+        nc, Ns = max(ncol, 0), self.problem.Nspace
+        fld = [f64(np.broadcast_to(np.asarray(a, dtype=np.float64), (nc, Ns))) for a in (B, gammaB, chiB)]
+        ncomp, alpha, strength, shift = zeeman.pack(patterns, self.problem.Nlines)
+        kk = None if ks is None else np.ascontiguousarray(np.asarray(ks).reshape(-1), dtype=np.int32)
+        nk = Ns if kk is None else kk.shape[0]
+        rf = np.empty((nc, len(names), 4, max(nla, 0), nk, mu.shape[0]), dtype=np.float64)
+        out = np.empty((nc, 4, max(nla, 0), mu.shape[0]), dtype=np.float64)
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        self.lib.check(self.lib.dll.lsx_hip_response_stokes(self._h, mu.shape[0], _ptr(mu), int(col0), ncol, int(la0), nla, _ptr(fld[0]),
+                                                            _ptr(fld[1]), _ptr(fld[2]), ip(ncomp), ip(alpha), _ptr(strength), _ptr(shift),
+                                                            bits, _ptr(amp), nk, None if kk is None else ip(kk), _ptr(rf), rf.nbytes,
+                                                            _ptr(out), out.nbytes))
+        return StokesResponse({w: rf[:, i] for i, w in enumerate(names)}, StokesRays(mu, la0, out[:, 0], out[:, 1], out[:, 2], out[:, 3]),
+                              np.arange(Ns, dtype=np.int32) if kk is None else kk, mu, la0, {w: float(amps[w]) for w in names})
 
     def _background_lib(self, entry):
         if not getattr(self.lib, 'has_background', False):

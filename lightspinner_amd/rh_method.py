@@ -527,6 +527,31 @@ class Context:
         pick = (lambda a: a[0, :, 0]) if scalar else (lambda a: a[0])
         return StokesRays(r.mus, r.la0, *(pick(getattr(r, w)) for w in StokesRays.FIELDS))
 
+    def compute_stokes_response(self, mus, B, gammaB, chiB, transition=None, la0=0, nla=None, parameters=('B', 'gammaB', 'chiB'),
+                                amplitudes=None, ks=None):
+        """Response functions of the emergent Stokes vector of compute_stokes to the field strength, inclination and azimuth at every
+        depth: RF_p[k] = (S(p_k + a_p / 2) - S(p_k - a_p / 2)) / a_p, per tesla resp. per radian.  In the field-free method this
+        is the change of one polarised formal solution: no NLTE solve (include/lsx_hip_stokes_response.h).  mus, B, gammaB, chiB,
+        transition, la0, nla and the Zeeman patterns as in compute_stokes; parameters: some of 'B', 'gammaB', 'chiB'; amplitudes:
+        a dict from those names to a_p (default 1e-3 T, 1e-3 rad); ks: the depths (None: all).
+        -> an object with .rf[name], each [4][nla][nk][nmu] ([4][nla][nk] for a float mu), .stokes (what compute_stokes returns),
+        .ks, .mus, .la0, .amplitudes.  Nothing of the context changes."""
+        from . import zeeman
+        from .problem import StokesRays, StokesResponse
+        self._cancel_lookahead()                  # (the library's J is the last accepted call's again)
+        self._push_host_edits()
+        if transition is not None:
+            if isinstance(transition, (int, np.integer)):
+                transition = [t for a in self.activeAtoms for t in a.trans][int(transition)]
+            la0, nla = int(transition.Nblue), int(transition.wavelength.shape[0])
+        patterns = [zeeman.zeeman_components(t.transModel) for a in self.activeAtoms for t in a.trans if t.isLine]
+        scalar = np.ndim(mus) == 0
+        r = self._engine.stokes_response(np.atleast_1d(np.asarray(mus, dtype=np.float64)), B, gammaB, chiB, patterns=patterns, la0=la0,
+                                         nla=nla, parameters=parameters, amplitudes=amplitudes, ks=ks)
+        pick = (lambda a: a[0, :, 0]) if scalar else (lambda a: a[0])
+        stokes = StokesRays(r.mus, r.la0, *(pick(getattr(r.stokes, w)) for w in StokesRays.FIELDS))
+        return StokesResponse({w: (a[0, ..., 0] if scalar else a[0]) for w, a in r.rf.items()}, stokes, r.ks, r.mus, r.la0, r.amplitudes)
+
     def compute_rates(self):
         """Radiative rates of every transition (rh_method.py:691-692) as ONE formal solution gives them from these populations and
         this J: -> an object with .Rij, .Rji, .Rji_ref, each [Ntrans][Nspace] in the order of `.transitions`
