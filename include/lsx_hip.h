@@ -83,5 +83,6 @@ int lsx_hip_poison_lds(int32_t device, int32_t rounds);
 #include "lsx_hip_boundary.h"
 #include "lsx_hip_stokes.h"
 #include "lsx_hip_stokes_response.h"
+#include "lsx_hip_fit.h"
 
 #endif /* LSX_HIP_H */

@@ -258,6 +258,18 @@ class LsxLibrary:
             d.lsx_hip_response_stokes.restype = C.c_int
             d.lsx_hip_response_stokes_work_cap.argtypes = [C.c_void_p, C.c_size_t]
             d.lsx_hip_response_stokes_work_cap.restype = C.c_int
+        self.has_fit_field = hasattr(d, 'lsx_hip_fit_field_normal')     # include/lsx_hip_fit.h
+        if self.has_fit_field:
+            ip32 = C.POINTER(C.c_int32)
+            head = [C.c_void_p, C.c_int32, _dp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, ip32, ip32, _dp, _dp, ip32, _dp, _dp, _dp]
+            d.lsx_hip_fit_field_normal.argtypes = head + [_dp, _dp, _dp, _dp, _dp, _dp, _dp]
+            d.lsx_hip_fit_field_normal.restype = C.c_int
+            d.lsx_hip_fit_field_chi2.argtypes = head + [_dp, _dp, _dp, _dp]
+            d.lsx_hip_fit_field_chi2.restype = C.c_int
+            d.lsx_hip_fit_field_step.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, ip32]
+            d.lsx_hip_fit_field_step.restype = C.c_int
+            d.lsx_hip_fit_field_work_cap.argtypes = [C.c_void_p, C.c_size_t]
+            d.lsx_hip_fit_field_work_cap.restype = C.c_int
         self.has_background = hasattr(d, 'lsx_hip_background')         # include/lsx_hip_background.h
         if self.has_background:
             ip32 = C.POINTER(C.c_int32)

@@ -17,6 +17,28 @@ namespace lsxd {
 extern thread_local std::string g_err;
 int fail(int code, const char* fmt, ...);    // records the message lsx_last_error returns; -> code
 struct FinalEnt;                             // an entry of the final passes' tables (lsx_final_dev.h)
+
+// What an internal caller of the Stokes pass or of its response hands over to keep a pass's result on the device (lsx_fit.hip): pass()
+// is called in the place of the pass's copy to the host, behind the pass's launches, with the pass's first column counted from the
+// call's col0, its number of columns and the pass's device array.  It queues its work on the context's stream; the caller of pass()
+// waits for the stream before the array is used again.
+struct PassSink {
+    virtual int pass(size_t b0, size_t nb, const double* d_result) = 0;
+protected:
+    ~PassSink() = default;
+};
+// the bodies of lsx_hip_stokes_rays (lsx_stokes.hip) and lsx_hip_response_stokes (lsx_stokes_response.hip); `who` heads the messages
+int stokes_rays_run(lsx_ctx* c, const char* who, int32_t nmu, const double* mu, int32_t col0, int32_t ncol, int32_t la0, int32_t nla,
+                    const double* B, const double* gammaB, const double* chiB, const int32_t* ncomp, const int32_t* alpha,
+                    const double* strength, const double* shift, double* out, size_t nbytes, PassSink* sink);
+int response_stokes_check(lsx_ctx* c, const char* who, int32_t nmu, const double* mu, int32_t col0, int32_t ncol, int32_t la0, int32_t nla,
+                          const double* B, const double* gammaB, const double* chiB, const int32_t* ncomp, const int32_t* alpha,
+                          const double* strength, const double* shift, uint32_t params, const double amplitude[3], int32_t nk,
+                          const int32_t* ks);
+int response_stokes_run(lsx_ctx* c, const char* who, int32_t nmu, const double* mu, int32_t col0, int32_t ncol, int32_t la0, int32_t nla,
+                        const double* B, const double* gammaB, const double* chiB, const int32_t* ncomp, const int32_t* alpha,
+                        const double* strength, const double* shift, uint32_t params, const double amplitude[3], int32_t nk,
+                        const int32_t* ks, double* rf, size_t rf_bytes, const size_t* stokes_bytes, PassSink* sink);
 } // namespace lsxd
 
 #define HIPCHK(expr)                                                                                    \
@@ -163,6 +185,10 @@ struct lsx_ctx : lsxd::LsxPlan {        // the plan (lsx_plan.h: dimensions, tab
     size_t stresp_tab_bytes = 0;
     double* d_stresp_work = nullptr;
     size_t stresp_work_doubles = 0, stresp_work_cap = 0;    // cap 0: the default of include/lsx_hip_stokes_response.h
+    // ... and of the field fit (lsx_fit.hip, include/lsx_hip_fit.h): basis, observation, weights, the kept Stokes vectors, the Jacobian
+    // and the sums of a group of columns, under fit_work_cap bytes
+    double* d_fit_work = nullptr;
+    size_t fit_work_doubles = 0, fit_work_cap = 0;          // cap 0: the default of include/lsx_hip_fit.h
     // Ng acceleration of the populations (lsx_ng.hip, include/lsx_hip_ng.h): off (order 0) unless lsx_hip_ng_configure turns it on
     int ng_order = 0, ng_delay = 0;
     double* d_ng_hist = nullptr;         // [col][order + 2][NLtot][k]: the stored populations, slot = the column's counter

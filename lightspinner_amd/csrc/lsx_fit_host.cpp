@@ -1,0 +1,106 @@
+// lsx_fit_host.cpp -- the arithmetic of lsx_fit_dev.h compiled for the CPU, on arrays handed over (tests and the sanitizer program only:
+// `make fithost`, `make fitsan`).  What lsx_fit.hip does in k_fit_jac, k_fit_reduce and k_fit_step, in the kernels' order: the same
+// lanes' parts, the same tree.  Built with -ffp-contract=off.
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "../../include/lsx_hip_fit.h"
+#include "lsx_fit_dev.h"
+
+using namespace lsxfit;
+
+namespace {
+
+int count_params(const int32_t* nnode)
+{
+    if (!nnode) return -1;
+    int64_t P = 0;
+    for (int a = 0; a < 3; ++a) {
+        if (nnode[a] < 0) return -1;
+        P += nnode[a];
+    }
+    return P >= 1 && P <= LSX_FIT_MAX_PARAMS ? (int)P : -1;
+}
+
+// sum_d w x y as a block of k_fit_reduce forms it
+double block_sum(int M, const double* w, const double* x, const double* y)
+{
+    double v[kReduceLanes];
+    for (int lane = 0; lane < kReduceLanes; ++lane) v[lane] = lane_sum(lane, M, w, x, y);
+    for (int s = kReduceLanes / 2; s > 0; s >>= 1)
+        for (int lane = 0; lane < s; ++lane) tree_step(v, lane, s);
+    return v[0];
+}
+
+} // namespace
+
+extern "C" {
+
+// the field of ncol columns from their nodes: basis [P][Ns], base [ncol][3][Ns] or null, nodes [ncol][P] -> field [ncol][3][Ns]
+int lsx_fit_host_expand(int32_t Ns, int32_t ncol, const int32_t* nnode, const double* basis, const double* base, const double* nodes,
+                        double* field)
+{
+    const int P = count_params(nnode);
+    if (P < 0 || Ns < 1 || ncol < 1 || !basis || !nodes || !field) return LSX_EINVAL;
+    const int row0[3] = {0, nnode[0], nnode[0] + nnode[1]};
+    for (size_t q = 0; q < (size_t)ncol; ++q)
+        for (int a = 0; a < 3; ++a)
+            for (int k = 0; k < Ns; ++k)
+                field[(q * 3 + a) * Ns + k] = expand(base ? base[(q * 3 + a) * Ns + k] : 0.0, nnode[a], nodes + q * P + row0[a],
+                                                     basis + (size_t)row0[a] * Ns, (size_t)Ns, (size_t)k);
+    return LSX_OK;
+}
+
+// One column's sums from its response and its Stokes vector: rf [npar][4][nla][Ns][nmu] (npar: the parameters with nodes, in the order
+// B, gammaB, chiB), S, obs, weight (or null) [4][nla][nmu], basis [P][Ns] -> chi2 [1], grad [P], hess [P][P].  grad and hess null
+// (then rf may be null too): chi2 alone.
+int lsx_fit_host_normal(int32_t Ns, int32_t nla, int32_t nmu, const int32_t* nnode, const double* rf, const double* S, const double* obs,
+                        const double* weight, const double* basis, double* chi2, double* grad, double* hess)
+{
+    const int P = count_params(nnode);
+    const bool normal = grad || hess;
+    if (P < 0 || Ns < 1 || nla < 1 || nmu < 1 || !S || !obs || !chi2 || (normal && (!grad || !hess || !rf || !basis))) return LSX_EINVAL;
+    const int M = 4 * nla * nmu;
+    std::vector<double> W((size_t)M), R((size_t)M), J(normal ? (size_t)P * M : 0);
+    for (int d = 0; d < M; ++d) residual(weight, obs, S, (size_t)d, W[d], R[d]);
+    *chi2 = block_sum(M, W.data(), R.data(), R.data());
+    if (!normal) return LSX_OK;
+    const size_t block = (size_t)Ns * nmu;
+    for (int a = 0, i = 0, j = 0; a < 3; ++a) {
+        for (int n = 0; n < nnode[a]; ++n, ++j)
+            for (int d = 0; d < M; ++d) {
+                const int sl = d / nmu, m = d - sl * nmu;
+                J[(size_t)j * M + d] = contract(rf + (size_t)i * 4 * nla * block + (size_t)sl * block + m, (size_t)nmu, basis + (size_t)j * Ns, Ns);
+            }
+        i += nnode[a] > 0;
+    }
+    for (int e = 0; e < entries(P) - 1; ++e) {
+        int a, b;
+        entry_pair(P, e, a, b);
+        const double sum = block_sum(M, W.data(), J.data() + (size_t)a * M, b >= 0 ? J.data() + (size_t)b * M : R.data());
+        if (b >= 0) hess[(size_t)a * P + b] = hess[(size_t)b * P + a] = sum;
+        else grad[a] = sum;
+    }
+    return LSX_OK;
+}
+
+// lsx_hip_fit_field_step on the CPU; delta [ncol][P] (may be null): the unclamped solution (NaN where status is 1)
+int lsx_fit_host_step(int32_t ncol, int32_t P, const double* hess, const double* grad, const double* lambda, const double* nodes,
+                      const double* lo, const double* hi, double* trial, double* predicted, int32_t* status, double* delta)
+{
+    if (ncol < 1 || P < 1 || P > LSX_FIT_MAX_PARAMS || !hess || !grad || !lambda || !nodes || !lo || !hi || !trial || !predicted || !status)
+        return LSX_EINVAL;
+    std::vector<double> w(step_doubles(P));
+    double* const d = w.data() + (size_t)P * (P + 1) / 2;
+    for (size_t c = 0; c < (size_t)ncol; ++c) {
+        const double* H = hess + c * P * P;
+        const int st = step_solve(P, H, grad + c * P, lambda[c], w.data(), 1);
+        for (int i = 0; i < P && delta; ++i) delta[c * P + i] = st ? NAN : d[i];
+        predicted[c] = step_finish(P, st, H, grad + c * P, nodes + c * P, lo, hi, d, 1, trial + c * P);
+        status[c] = st;
+    }
+    return LSX_OK;
+}
+
+} // extern "C"

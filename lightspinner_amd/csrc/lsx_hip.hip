@@ -1278,7 +1278,7 @@ void lsx_destroy(lsx_ctx* c)
                     c->d_sa_atoms, c->d_sa_lines, c->d_sa_colls, c->d_sa_spl, c->d_sa_levE, c->d_sa_levg, c->d_sa_levnD, c->d_sa_levdZ,
                     c->d_vBroad, c->d_aDamp, c->d_vlos, c->d_prof_kind, c->d_final_ptr, c->d_final_tile, c->d_final_row, c->d_final_ent,
                     c->d_rates_work, c->d_losses_work, c->d_losses_wnu, c->d_depth_work, c->d_spec_tab, c->d_spec_work,
-                    c->d_stokes_tab, c->d_stokes_work, c->d_stresp_tab, c->d_stresp_work};
+                    c->d_stokes_tab, c->d_stokes_work, c->d_stresp_tab, c->d_stresp_work, c->d_fit_work};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     for (int v = 0; v < LSX_FGC_LISTS; ++v) if (c->d_fast_cols[v]) (void)hipFree(c->d_fast_cols[v]);

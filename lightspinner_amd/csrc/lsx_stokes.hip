@@ -193,14 +193,15 @@ extern "C" int lsx_hip_stokes_rays_work_cap(lsx_ctx* c, size_t nbytes)
     return LSX_OK;
 }
 
-extern "C" int lsx_hip_stokes_rays(lsx_ctx* c, int32_t nmu, const double* mu, int32_t col0, int32_t ncol, int32_t la0, int32_t nla,
-                                   const double* B, const double* gammaB, const double* chiB,
-                                   const int32_t* ncomp, const int32_t* alpha, const double* strength, const double* shift,
-                                   double* out, size_t nbytes)
+// The body of lsx_hip_stokes_rays.  sink null: the entry itself -- every pass is copied to out.  An internal caller (lsx_fit.hip) hands a
+// sink instead and out null: a pass's result stays in the pass's device array and the sink is called in the copy's place.
+int lsxd::stokes_rays_run(lsx_ctx* c, const char* who, int32_t nmu, const double* mu, int32_t col0, int32_t ncol, int32_t la0, int32_t nla,
+                          const double* B, const double* gammaB, const double* chiB,
+                          const int32_t* ncomp, const int32_t* alpha, const double* strength, const double* shift,
+                          double* out, size_t nbytes, PassSink* sink)
 {
-    const char* who = "lsx_hip_stokes_rays";
     // ---- everything is checked on the host before anything is launched ----
-    if (!c || !mu || !B || !gammaB || !chiB || !out) return fail(LSX_EINVAL, "%s: null argument", who);
+    if (!c || !mu || !B || !gammaB || !chiB || (!out && !sink)) return fail(LSX_EINVAL, "%s: null argument", who);
     if (c->Nlines && !ncomp) return fail(LSX_EINVAL, "%s: null ncomp (one count per line; zeros for no pattern)", who);
     int rc = final_check_angles(who, nmu, mu);
     if (!rc) rc = final_check_range(c, who, col0, ncol);
@@ -209,7 +210,7 @@ extern "C" int lsx_hip_stokes_rays(lsx_ctx* c, int32_t nmu, const double* mu, in
     if (la0 < 0 || (int64_t)la0 + nla > c->Nspect)
         return fail(LSX_EINVAL, "%s: wavelengths [%d, %d) are outside the grid's %d", who, (int)la0, (int)la0 + (int)nla, c->Nspect);
     const size_t plane = (size_t)nla * nmu, per = 4 * plane;
-    if (nbytes != (size_t)ncol * per * 8) return fail(LSX_EINVAL, "%s: nbytes does not match [ncol][4][nla][nmu]", who);
+    if (!sink && nbytes != (size_t)ncol * per * 8) return fail(LSX_EINVAL, "%s: nbytes does not match [ncol][4][nla][nmu]", who);
     const int Ns = c->Nspace;
     std::string msg;
     if ((rc = lsxst::check_field((size_t)ncol * Ns, B, gammaB, chiB, msg))) return fail(rc, "%s: %s", who, msg.c_str());
@@ -308,8 +309,21 @@ extern "C" int lsx_hip_stokes_rays(lsx_ctx* c, int32_t nmu, const double* mu, in
             launch_chunk<1>(p, grid, lds, c->stream);
         }
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(out + b0 * per, d_out, nb * per * 8, hipMemcpyDeviceToHost, c->stream));
+        if (sink) {
+            if ((rc = sink->pass(b0, nb, d_out))) return rc;
+        } else {
+            HIPCHK(hipMemcpyAsync(out + b0 * per, d_out, nb * per * 8, hipMemcpyDeviceToHost, c->stream));
+        }
         HIPCHK(hipStreamSynchronize(c->stream));       // the arrays are re-used by the next pass
     }
     return LSX_OK;
+}
+
+extern "C" int lsx_hip_stokes_rays(lsx_ctx* c, int32_t nmu, const double* mu, int32_t col0, int32_t ncol, int32_t la0, int32_t nla,
+                                   const double* B, const double* gammaB, const double* chiB,
+                                   const int32_t* ncomp, const int32_t* alpha, const double* strength, const double* shift,
+                                   double* out, size_t nbytes)
+{
+    return stokes_rays_run(c, "lsx_hip_stokes_rays", nmu, mu, col0, ncol, la0, nla, B, gammaB, chiB, ncomp, alpha, strength, shift, out, nbytes,
+                           nullptr);
 }

@@ -218,15 +218,15 @@ extern "C" int lsx_hip_response_stokes_work_cap(lsx_ctx* c, size_t nbytes)
     return LSX_OK;
 }
 
-extern "C" int lsx_hip_response_stokes(lsx_ctx* c, int32_t nmu, const double* mu, int32_t col0, int32_t ncol, int32_t la0, int32_t nla,
-                                       const double* B, const double* gammaB, const double* chiB,
-                                       const int32_t* ncomp, const int32_t* alpha, const double* strength, const double* shift,
-                                       uint32_t params, const double amplitude[3], int32_t nk, const int32_t* ks,
-                                       double* rf, size_t rf_bytes, double* stokes, size_t stokes_bytes)
+// The argument rules of lsx_hip_response_stokes but the byte counts; nothing is launched.  (lsx_fit.hip asks them of its expanded
+// field before its first launch.)
+int lsxd::response_stokes_check(lsx_ctx* c, const char* who, int32_t nmu, const double* mu, int32_t col0, int32_t ncol, int32_t la0,
+                                int32_t nla, const double* B, const double* gammaB, const double* chiB, const int32_t* ncomp,
+                                const int32_t* alpha, const double* strength, const double* shift, uint32_t params,
+                                const double amplitude[3], int32_t nk, const int32_t* ks)
 {
-    const char* who = "lsx_hip_response_stokes";
-    // ---- everything is checked on the host before anything is launched: first what lsx_hip_stokes_rays checks, in its order ----
-    if (!c || !mu || !B || !gammaB || !chiB || !rf) return fail(LSX_EINVAL, "%s: null argument", who);
+    // ---- first what lsx_hip_stokes_rays checks, in its order ----
+    if (!c || !mu || !B || !gammaB || !chiB) return fail(LSX_EINVAL, "%s: null argument", who);
     if (c->Nlines && !ncomp) return fail(LSX_EINVAL, "%s: null ncomp (one count per line; zeros for no pattern)", who);
     int rc = final_check_angles(who, nmu, mu);
     if (!rc) rc = final_check_range(c, who, col0, ncol);
@@ -248,15 +248,36 @@ extern "C" int lsx_hip_response_stokes(lsx_ctx* c, int32_t nmu, const double* mu
     // ---- ... then the response's own rules ----
     if ((rc = lsxst::check_response(params, amplitude, Ns, nk, ks, (size_t)ncol, col0, B, msg))) return fail(rc, "%s: %s", who, msg.c_str());
     int par[3] = {0, 0, 0};
-    const int npar = lsxst::response_params(params, par);
-    const int nvar = 1 + 2 * npar;
-    const int nkk = ks ? nk : Ns;
-    const size_t plane = (size_t)nla * nmu, per_s = 4 * plane, per_rf = (size_t)npar * 4 * plane * nkk;
-    if (rf_bytes != (size_t)ncol * per_rf * 8) return fail(LSX_EINVAL, "%s: rf_bytes does not match [ncol][npar][4][nla][nk][nmu]", who);
-    if (stokes && stokes_bytes != (size_t)ncol * per_s * 8) return fail(LSX_EINVAL, "%s: stokes_bytes does not match [ncol][4][nla][nmu]", who);
+    const int nvar = 1 + 2 * lsxst::response_params(params, par);
     if ((int64_t)Ns * nvar > 65535 || nmu > 65535)
         return fail(LSX_EUNSUPPORTED, "%s: Nspace x (1 + 2 parameters) = %lld or nmu = %d is above a grid's 65535", who,
                     (long long)Ns * nvar, (int)nmu);
+    return LSX_OK;
+}
+
+// The body of lsx_hip_response_stokes without its `stokes`.  sink null: the entry itself -- every pass is copied to rf.  An internal
+// caller (lsx_fit.hip) hands a sink instead and rf null: a pass's rf stays in the pass's device array and the sink is called in the
+// copy's place.  stokes_bytes: null, or the byte count of the entry's `stokes` to be checked with the others.
+int lsxd::response_stokes_run(lsx_ctx* c, const char* who, int32_t nmu, const double* mu, int32_t col0, int32_t ncol, int32_t la0,
+                              int32_t nla, const double* B, const double* gammaB, const double* chiB, const int32_t* ncomp,
+                              const int32_t* alpha, const double* strength, const double* shift, uint32_t params,
+                              const double amplitude[3], int32_t nk, const int32_t* ks, double* rf, size_t rf_bytes,
+                              const size_t* stokes_bytes, PassSink* sink)
+{
+    // ---- everything is checked on the host before anything is launched ----
+    if (!rf && !sink) return fail(LSX_EINVAL, "%s: null argument", who);
+    int rc = response_stokes_check(c, who, nmu, mu, col0, ncol, la0, nla, B, gammaB, chiB, ncomp, alpha, strength, shift, params, amplitude,
+                                   nk, ks);
+    if (rc) return rc;
+    const int Ns = c->Nspace;
+    std::string msg;
+    int par[3] = {0, 0, 0};
+    const int npar = lsxst::response_params(params, par);
+    const int nvar = 1 + 2 * npar;
+    const int nkk = ks ? nk : Ns;
+    const size_t plane = (size_t)nla * nmu, per_rf = (size_t)npar * 4 * plane * nkk;
+    if (!sink && rf_bytes != (size_t)ncol * per_rf * 8) return fail(LSX_EINVAL, "%s: rf_bytes does not match [ncol][npar][4][nla][nk][nmu]", who);
+    if (stokes_bytes && *stokes_bytes != (size_t)ncol * 4 * plane * 8) return fail(LSX_EINVAL, "%s: stokes_bytes does not match [ncol][4][nla][nmu]", who);
 
     // the patterns of the lines that are active somewhere in the window
     std::vector<uint8_t> wanted(std::max(1, c->Nlines), 0);
@@ -365,9 +386,27 @@ extern "C" int lsx_hip_response_stokes(lsx_ctx* c, int32_t nmu, const double* mu
         p.mu0 = 0;
         hipLaunchKernelGGL(k_response_walk, dim3((unsigned)nblk, (unsigned)nb, (unsigned)nmu), dim3(64), lds_walk, c->stream, p);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(rf + b0 * per_rf, d_rf, nb * per_rf * 8, hipMemcpyDeviceToHost, c->stream));
+        if (sink) {
+            if ((rc = sink->pass(b0, nb, d_rf))) return rc;
+        } else {
+            HIPCHK(hipMemcpyAsync(rf + b0 * per_rf, d_rf, nb * per_rf * 8, hipMemcpyDeviceToHost, c->stream));
+        }
         HIPCHK(hipStreamSynchronize(c->stream));       // the arrays are re-used by the next pass
     }
+    return LSX_OK;
+}
+
+extern "C" int lsx_hip_response_stokes(lsx_ctx* c, int32_t nmu, const double* mu, int32_t col0, int32_t ncol, int32_t la0, int32_t nla,
+                                       const double* B, const double* gammaB, const double* chiB,
+                                       const int32_t* ncomp, const int32_t* alpha, const double* strength, const double* shift,
+                                       uint32_t params, const double amplitude[3], int32_t nk, const int32_t* ks,
+                                       double* rf, size_t rf_bytes, double* stokes, size_t stokes_bytes)
+{
+    const char* who = "lsx_hip_response_stokes";
+    if (!rf) return fail(LSX_EINVAL, "%s: null argument", who);
+    const int rc = response_stokes_run(c, who, nmu, mu, col0, ncol, la0, nla, B, gammaB, chiB, ncomp, alpha, strength, shift, params, amplitude,
+                                       nk, ks, rf, rf_bytes, stokes ? &stokes_bytes : nullptr, nullptr);
+    if (rc) return rc;
     // The vector of the call's own field comes from the Stokes pass itself, so that it has that pass's bits by construction.  The
     // walk up forms the same vector through the same functions (the host build's is bit for bit lsx_stokes_host_window's), but in
     // another kernel the device compiler contracts products and sums into fused operations differently: measured on an MI355X, a

@@ -293,3 +293,52 @@ def advance_time_columns(engine, dt, nsteps=1, dJ_tol=2e-3, dPops_tol=1e-3, max_
             engine.set_active_columns(active)
         engine.set_active_columns(None)
     return counts
+
+
+def fit_field_columns(backend, obs, mus, basis, nodes0, nnode, weight=None, base=None, lo=None, hi=None, lambda0=1e-2, factor=10.0,
+                      lambda_min=1e-9, lambda_max=1e8, tol=1e-12, max_iter=30, log=None, **call):
+    """Levenberg-Marquardt fit of the field vector of many independent columns to observed Stokes profiles (include/lsx_hip_fit.h).
+    backend: anything with fit_field_normal, fit_field_chi2 and fit_field_step as Engine has them (an Engine is one).  obs
+    [ncol][4][nla][nmu]; basis [P][Nspace], nnode, nodes0 [ncol][P], weight, base as in Engine.fit_field_normal; lo, hi [P]: bounds
+    of the node values; **call: what else the backend's two field calls take (patterns, la0, nla, col0, ncol, amplitudes for the
+    normal equations).  Per iteration and column: the normal equations at the nodes, the damped step, chi2 of the trial; where chi2
+    fell the trial is accepted and lambda /= factor (not below lambda_min), otherwise lambda *= factor.  A column is done when a
+    trial moved chi2 by less than tol x the chi2 the column started from (the trial is still accepted if it is lower), when lambda
+    passes lambda_max, or at max_iter; a done column is frozen: its nodes no longer move.  This loop compares and scales scalars;
+    every sum and every solve is the backend's.  -> fit.FieldFit."""
+    from .fit import CONVERGED, LAMBDA_CEILING, MAX_ITER, FieldFit
+    nodes = np.array(np.atleast_2d(np.asarray(nodes0, dtype=np.float64)), dtype=np.float64)
+    ncol = nodes.shape[0]
+    chi2_call = {k: v for k, v in call.items() if k != 'amplitudes'}
+    lam = np.full(ncol, float(lambda0))
+    active = np.ones(ncol, dtype=bool)
+    status = np.full(ncol, MAX_ITER, dtype=np.int32)
+    iterations = np.zeros(ncol, dtype=np.int64)
+    chi2, field = backend.fit_field_chi2(mus, basis, nnode, nodes, obs, weight=weight, base=base, **chi2_call)
+    chi2 = np.array(chi2, dtype=np.float64)
+    first = chi2.copy()
+    history = [chi2.copy()]
+    for it in range(1, int(max_iter) + 1):
+        if not active.any():
+            break
+        ne = backend.fit_field_normal(mus, basis, nnode, nodes, obs, weight=weight, base=base, **call)
+        trial, _, st = backend.fit_field_step(ne.hess, ne.grad, lam, nodes, lo, hi)
+        trial = np.where(active[:, None], trial, nodes)               # a frozen column is asked about its own nodes
+        c_trial, f_trial = backend.fit_field_chi2(mus, basis, nnode, trial, obs, weight=weight, base=base, **chi2_call)
+        with np.errstate(invalid='ignore'):
+            accept = active & (st == 0) & (c_trial < chi2)
+            settled = active & (st == 0) & (np.abs(c_trial - chi2) < tol * first)
+        iterations[active] = it
+        nodes[accept] = trial[accept]
+        field[accept] = f_trial[accept]
+        chi2[accept] = c_trial[accept]
+        lam = np.where(accept, np.maximum(lam / factor, lambda_min), np.where(active, lam * factor, lam))
+        settled |= active & (chi2 == 0.0)
+        ceiling = active & ~settled & (lam > lambda_max)
+        status[settled] = CONVERGED
+        status[ceiling] = LAMBDA_CEILING
+        active &= ~(settled | ceiling)
+        history.append(chi2.copy())
+        if log:
+            log('Fit iteration %.3d: %d of %d columns still iterating, largest chi2 %.6e' % (it, int(active.sum()), ncol, float(chi2.max())))
+    return FieldFit(nodes, field, chi2, np.array(history), lam, iterations, status, nnode)

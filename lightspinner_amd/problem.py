@@ -730,6 +730,87 @@ class Engine:
         return StokesResponse({w: rf[:, i] for i, w in enumerate(names)}, StokesRays(mu, la0, out[:, 0], out[:, 1], out[:, 2], out[:, 3]),
                               np.arange(Ns, dtype=np.int32) if kk is None else kk, mu, la0, {w: float(amps[w]) for w in names})
 
+    def _fit_args(self, who, mus, basis, nnode, nodes, obs, weight, base, patterns, la0, nla, col0, ncol, work_cap_bytes):
+        from . import zeeman
+        if not getattr(self.lib, 'has_fit_field', False):
+            raise NotImplementedError('%s (%s) does not export lsx_hip_%s: the field fit is computed by the HIP library only'
+                                      % (self.lib.path, self.lib.backend, who))
+        if work_cap_bytes is not None:
+            self.lib.check(self.lib.dll.lsx_hip_fit_field_work_cap(self._h, int(work_cap_bytes)))
+        mu = f64(np.atleast_1d(np.asarray(mus, dtype=np.float64)).reshape(-1))
+        ncol = self.ncol - int(col0) if ncol is None else int(ncol)
+        nla = self.problem.Nspect - int(la0) if nla is None else int(nla)
+        nc, Ns = max(ncol, 0), self.problem.Nspace
+        nn = np.ascontiguousarray(np.asarray(nnode).reshape(-1), dtype=np.int32)
+        if nn.shape[0] != 3:
+            raise ValueError('%s: nnode must hold three counts (B, gammaB, chiB)' % who)
+        P = max(int(nn.clip(min=0).sum()), 1)
+        bas = f64(np.asarray(basis, dtype=np.float64).reshape(-1, Ns))
+        if bas.shape[0] != int(nn.sum()):
+            raise ValueError('%s: basis has %d rows, nnode sums to %d' % (who, bas.shape[0], int(nn.sum())))
+        x = f64(np.broadcast_to(np.asarray(nodes, dtype=np.float64), (nc, P)))
+        shape = (nc, 4, max(nla, 0), mu.shape[0])
+        ob = f64(np.asarray(obs, dtype=np.float64).reshape(shape))
+        wt = None if weight is None else f64(np.broadcast_to(np.asarray(weight, dtype=np.float64), shape))
+        bs = None if base is None else f64(np.broadcast_to(np.asarray(base, dtype=np.float64), (nc, 3, Ns)))
+        ncomp, alpha, strength, shift = zeeman.pack(patterns, self.problem.Nlines)
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        keep = (mu, nn, bas, x, ob, wt, bs, ncomp, alpha, strength, shift)
+        head = [self._h, mu.shape[0], _ptr(mu), int(col0), ncol, int(la0), nla, ip(ncomp), ip(alpha), _ptr(strength), _ptr(shift), ip(nn),
+                _ptr(bas), None if bs is None else _ptr(bs), _ptr(x)]
+        return head, keep, _ptr(ob), None if wt is None else _ptr(wt), nc, P, Ns
+
+    def fit_field_normal(self, mus, basis, nnode, nodes, obs, weight=None, base=None, patterns=None, la0=0, nla=None, col0=0, ncol=None,
+                         amplitudes=None, work_cap_bytes=None):
+        """chi2 and the normal equations of the fit of the field vector to observed Stokes profiles at `nodes`
+        (include/lsx_hip_fit.h, lsx_hip_fit_field_normal): the field of a column is base_p + sum_n nodes[p][n] basis_p[n] for p of
+        B, gammaB, chiB; nnode: the three node counts (0: not fitted); basis [P][Nspace], the rows of B first; nodes [ncol][P];
+        base [ncol][3][Nspace] or None; obs, weight [ncol][4][nla][nmu] (weight None: 1).  mus, patterns, la0, nla, col0, ncol as in
+        stokes_rays; amplitudes as in stokes_response.  The response never leaves the device.  Read-only.
+        -> fit.FieldNormal (.chi2, .grad, .hess, .field).  Only the HIP library computes it."""
+        from .fit import FieldNormal
+        head, keep, ob, wt, nc, P, Ns = self._fit_args('fit_field_normal', mus, basis, nnode, nodes, obs, weight, base, patterns, la0, nla,
+                                                       col0, ncol, work_cap_bytes)
+        amps = dict(StokesResponse.DEFAULT_AMPLITUDES)
+        amps.update(amplitudes or {})
+        amp = f64(np.array([amps[w] for w in StokesResponse.PARAMETERS], dtype=np.float64))
+        chi2, grad, hess = np.empty(nc), np.empty((nc, P)), np.empty((nc, P, P))
+        field = np.empty((nc, 3, Ns))
+        self.lib.check(self.lib.dll.lsx_hip_fit_field_normal(*head, _ptr(amp), ob, wt, _ptr(chi2), _ptr(grad), _ptr(hess), _ptr(field)))
+        del keep
+        return FieldNormal(chi2, grad, hess, field)
+
+    def fit_field_chi2(self, mus, basis, nnode, nodes, obs, weight=None, base=None, patterns=None, la0=0, nla=None, col0=0, ncol=None,
+                       work_cap_bytes=None):
+        """chi2 of the field expanded from `nodes` (lsx_hip_fit_field_chi2): one Stokes pass and the reduction of fit_field_normal --
+        its chi2, bit for bit.  Arguments as fit_field_normal.  -> (chi2 [ncol], field [ncol][3][Nspace])."""
+        head, keep, ob, wt, nc, P, Ns = self._fit_args('fit_field_chi2', mus, basis, nnode, nodes, obs, weight, base, patterns, la0, nla,
+                                                       col0, ncol, work_cap_bytes)
+        chi2, field = np.empty(nc), np.empty((nc, 3, Ns))
+        self.lib.check(self.lib.dll.lsx_hip_fit_field_chi2(*head, ob, wt, _ptr(chi2), _ptr(field)))
+        del keep
+        return chi2, field
+
+    def fit_field_step(self, hess, grad, lam, nodes, lo=None, hi=None):
+        """The damped step per column (lsx_hip_fit_field_step): (hess + lam diag(hess)) delta = grad by Cholesky on the device,
+        trial = clip(nodes + delta, lo, hi), predicted = 2 d.grad - d.hess d for d = trial - nodes.  hess [ncol][P][P], grad, nodes
+        [ncol][P], lam [ncol] or a scalar, lo, hi [P] or None (no bound).  -> (trial [ncol][P], predicted [ncol], status [ncol]:
+        1 where the system is singular or holds a NaN; then trial = nodes, predicted = 0)."""
+        if not getattr(self.lib, 'has_fit_field', False):
+            raise NotImplementedError('%s (%s) does not export lsx_hip_fit_field_step: the field fit is computed by the HIP library '
+                                      'only' % (self.lib.path, self.lib.backend))
+        g = f64(np.atleast_2d(np.asarray(grad, dtype=np.float64)))
+        nc, P = g.shape
+        H = f64(np.asarray(hess, dtype=np.float64).reshape(nc, P, P))
+        x = f64(np.broadcast_to(np.asarray(nodes, dtype=np.float64), (nc, P)))
+        lm = f64(np.broadcast_to(np.asarray(lam, dtype=np.float64), (nc,)))
+        lo_ = f64(np.broadcast_to(np.asarray(-np.inf if lo is None else lo, dtype=np.float64), (P,)))
+        hi_ = f64(np.broadcast_to(np.asarray(np.inf if hi is None else hi, dtype=np.float64), (P,)))
+        trial, pred, status = np.empty((nc, P)), np.empty(nc), np.empty(nc, dtype=np.int32)
+        self.lib.check(self.lib.dll.lsx_hip_fit_field_step(self._h, nc, P, _ptr(H), _ptr(g), _ptr(lm), _ptr(x), _ptr(lo_), _ptr(hi_),
+                                                           _ptr(trial), _ptr(pred), status.ctypes.data_as(C.POINTER(C.c_int32))))
+        return trial, pred, status
+
     def _background_lib(self, entry):
         if not getattr(self.lib, 'has_background', False):
             raise NotImplementedError('%s (%s) does not export %s: the equation of state and the background opacity are computed '

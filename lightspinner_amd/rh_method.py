@@ -552,6 +552,39 @@ class Context:
         stokes = StokesRays(r.mus, r.la0, *(pick(getattr(r.stokes, w)) for w in StokesRays.FIELDS))
         return StokesResponse({w: (a[0, ..., 0] if scalar else a[0]) for w, a in r.rf.items()}, stokes, r.ks, r.mus, r.la0, r.amplitudes)
 
+    def fit_field(self, mus, obs, transition=None, basis=None, start=None, nnode=None, weight=None, base=None, la0=0, nla=None,
+                  amplitudes=None, **loop):
+        """Fit the magnetic field vector to observed Stokes profiles obs [4][nla][nmu] ([4][nla] for a float mu) by the field-free
+        method: these populations and this J, Levenberg-Marquardt on the node values of field_p = base_p + sum_n x[p][n] basis_p[n]
+        (drivers.fit_field_columns on the context's engine; include/lsx_hip_fit.h).  basis [P][Nspace] with nnode = the node counts of
+        (B, gammaB, chiB), or a dict from those names to row sets (fit.hat_basis makes them); start: the first node values [P];
+        weight as obs or None; base [3][Nspace] or None; mus, transition, la0, nla and the Zeeman patterns as in compute_stokes;
+        amplitudes as in compute_stokes_response; **loop: lo, hi, lambda0, factor, lambda_min, lambda_max, tol, max_iter, log.
+        -> fit.FieldFit without the column axis.  Nothing of the context changes."""
+        from . import zeeman
+        from .drivers import fit_field_columns
+        from .fit import FieldFit, stack_basis
+        self._cancel_lookahead()                  # (the library's J is the last accepted call's again)
+        self._push_host_edits()
+        if transition is not None:
+            if isinstance(transition, (int, np.integer)):
+                transition = [t for a in self.activeAtoms for t in a.trans][int(transition)]
+            la0, nla = int(transition.Nblue), int(transition.wavelength.shape[0])
+        if isinstance(basis, dict):
+            basis, nnode = stack_basis(**basis)
+        if basis is None or start is None or nnode is None:
+            raise ValueError('fit_field: basis (with nnode, or as a dict per parameter) and start are needed')
+        patterns = [zeeman.zeeman_components(t.transModel) for a in self.activeAtoms for t in a.trans if t.isLine]
+        mu = np.atleast_1d(np.asarray(mus, dtype=np.float64))
+        nla_ = self._engine.problem.Nspect - int(la0) if nla is None else int(nla)
+        shape = (1, 4, nla_, mu.shape[0])
+        r = fit_field_columns(self._engine, np.asarray(obs, dtype=np.float64).reshape(shape), mu, basis, np.asarray(start)[None, :], nnode,
+                              weight=None if weight is None else np.broadcast_to(np.asarray(weight, dtype=np.float64).reshape(
+                                  (1, 4, nla_, -1) if np.ndim(weight) else ()), shape),
+                              base=None if base is None else np.asarray(base, dtype=np.float64)[None], patterns=patterns, la0=la0, nla=nla_,
+                              amplitudes=amplitudes, **loop)
+        return FieldFit(r.nodes[0], r.field[0], r.chi2[0], r.history[:, 0], r.lam[0], r.iterations[0], r.status[0], r.nnode)
+
     def compute_rates(self):
         """Radiative rates of every transition (rh_method.py:691-692) as ONE formal solution gives them from these populations and
         this J: -> an object with .Rij, .Rji, .Rji_ref, each [Ntrans][Nspace] in the order of `.transitions`
