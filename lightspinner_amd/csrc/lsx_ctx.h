@@ -27,18 +27,70 @@ struct PassSink {
 protected:
     ~PassSink() = default;
 };
+// What a Stokes pass is asked for, as lsx_hip_stokes_rays takes it (include/lsx_hip_stokes.h): angles, columns, window of the merged
+// grid, the field of the call's columns ([ncol][Nspace] each) and the Zeeman patterns of the lines.  The entries build it from their
+// arguments, in this order; lsx_fit.hip builds one per group of columns
+struct StokesCall {
+    int32_t nmu;
+    const double* mu;
+    int32_t col0, ncol, la0, nla;
+    const double *B, *gammaB, *chiB;
+    const int32_t *ncomp, *alpha;
+    const double *strength, *shift;
+};
 // the bodies of lsx_hip_stokes_rays (lsx_stokes.hip) and lsx_hip_response_stokes (lsx_stokes_response.hip); `who` heads the messages
-int stokes_rays_run(lsx_ctx* c, const char* who, int32_t nmu, const double* mu, int32_t col0, int32_t ncol, int32_t la0, int32_t nla,
-                    const double* B, const double* gammaB, const double* chiB, const int32_t* ncomp, const int32_t* alpha,
-                    const double* strength, const double* shift, double* out, size_t nbytes, PassSink* sink);
-int response_stokes_check(lsx_ctx* c, const char* who, int32_t nmu, const double* mu, int32_t col0, int32_t ncol, int32_t la0, int32_t nla,
-                          const double* B, const double* gammaB, const double* chiB, const int32_t* ncomp, const int32_t* alpha,
-                          const double* strength, const double* shift, uint32_t params, const double amplitude[3], int32_t nk,
+int stokes_rays_run(lsx_ctx* c, const char* who, const StokesCall& s, double* out, size_t nbytes, PassSink* sink);
+int response_stokes_check(lsx_ctx* c, const char* who, const StokesCall& s, uint32_t params, const double amplitude[3], int32_t nk,
                           const int32_t* ks);
-int response_stokes_run(lsx_ctx* c, const char* who, int32_t nmu, const double* mu, int32_t col0, int32_t ncol, int32_t la0, int32_t nla,
-                        const double* B, const double* gammaB, const double* chiB, const int32_t* ncomp, const int32_t* alpha,
-                        const double* strength, const double* shift, uint32_t params, const double amplitude[3], int32_t nk,
+int response_stokes_run(lsx_ctx* c, const char* who, const StokesCall& s, uint32_t params, const double amplitude[3], int32_t nk,
                         const int32_t* ks, double* rf, size_t rf_bytes, const size_t* stokes_bytes, PassSink* sink);
+// What the two passes share on the host (lsx_stokes.hip).  The argument rules every Stokes call answers to, in the order
+// lsx_hip_stokes_rays always tested them, in two halves because that entry tests its byte count between them: what the call says
+// about itself (null arguments, ncomp, angles, columns, window) ...
+int stokes_check_call(const lsx_ctx* c, const char* who, const StokesCall& s);
+// ... and what it asks of the field, the patterns and the state of its columns
+int stokes_check_state(const lsx_ctx* c, const char* who, const StokesCall& s);
+// the patterns of the lines that are active somewhere in the window, packed for the device (lsx_stokes_prep.h, pack_patterns)
+int stokes_patterns(const lsx_ctx* c, const char* who, const StokesCall& s, std::vector<int32_t>& pat_line, std::vector<double>& pat_tab);
+// the field of a pass: columns [b0, b0 + nb) of the call's three arrays to d_field, nb * Nspace doubles each, that far apart
+int stokes_upload_field(lsx_ctx* c, const StokesCall& s, size_t b0, size_t nb, double* d_field);
+
+// The device buffers that grow with the calls: the work arrays of the passes under a cap, and the tables of a call.  One per purpose;
+// they never share storage (the fit holds its own while the Stokes and the response pass run inside it, the response entry runs the
+// Stokes pass behind its own).  lsx_destroy releases all of lsx_ctx::buf: a new buffer is a new name here and nothing else
+enum FinalBuf {
+    // the work arrays of lsx_hip_radiative_rates (lsx_rates.hip), allocated at first use, under the cap (0: include/lsx_hip_rates.h's)
+    BUF_RATES_WORK,
+    // ... of lsx_hip_radiative_losses (lsx_losses.hip; cap 0: the default of include/lsx_hip_losses.h)
+    BUF_LOSSES_WORK,
+    // ... of lsx_hip_depth_rays (lsx_depth.hip; cap 0: the default of include/lsx_hip_depth.h)
+    BUF_DEPTH_WORK,
+    // ... and of lsx_hip_spectrum (lsx_spectrum.hip): the tables of a call (they depend on the call's wavelengths: rebuilt per call,
+    // the buffer grows as needed) and the arrays of a pass (allocated at first use; cap 0: the default of include/lsx_hip_spectrum.h)
+    BUF_SPEC_TAB, BUF_SPEC_WORK,
+    // ... and of lsx_hip_stokes_rays (lsx_stokes.hip): the Zeeman pattern tables of a call (rebuilt per call, the buffer grows as
+    // needed) and the angles, the field and the result of a pass (allocated at first use; cap 0: include/lsx_hip_stokes.h's)
+    BUF_STOKES_TAB, BUF_STOKES_WORK,
+    // ... and of lsx_hip_response_stokes (lsx_stokes_response.hip): pattern tables and requested depths of a call, and the arrays of
+    // a pass (angles, field, nodes, kept states, the two results; cap 0: the default of include/lsx_hip_stokes_response.h)
+    BUF_STRESP_TAB, BUF_STRESP_WORK,
+    // ... and of the field fit (lsx_fit.hip): basis, observation, weights, the kept Stokes vectors, the Jacobian and the sums of a
+    // group of columns (cap 0: the default of include/lsx_hip_fit.h)
+    BUF_FIT_WORK,
+    BUF_COUNT
+};
+struct GrowBuf {
+    char* p = nullptr;
+    size_t bytes = 0;
+    size_t cap = 0;             // what the buffer's unit keeps its passes under, in bytes; 0: the default of the unit's header
+    template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
+    // at least nbytes: nothing if they are there; else behind the context's stream the old array goes and a new one is made (a failed
+    // allocation leaves the buffer empty)
+    int reserve(lsx_ctx* c, size_t nbytes);
+    // the whole of a unit's _work_cap entry `who`: the array goes, the next call allocates under the new cap
+    static int set_cap(lsx_ctx* c, FinalBuf b, const char* who, size_t nbytes);
+    void release();             // lsx_destroy
+};
 } // namespace lsxd
 
 #define HIPCHK(expr)                                                                                    \
@@ -156,39 +208,11 @@ struct lsx_ctx : lsxd::LsxPlan {        // the plan (lsx_plan.h: dimensions, tab
     // column-independent tables of the final passes over the context's own grid, made on first use (final_tables, lsx_final_host.h)
     int32_t *d_final_ptr = nullptr, *d_final_tile = nullptr, *d_final_row = nullptr;
     lsxd::FinalEnt* d_final_ent = nullptr;
-    // the work arrays of lsx_hip_radiative_rates (lsx_rates.hip), allocated at first use, under rates_work_cap bytes
-    double* d_rates_work = nullptr;
-    size_t rates_work_doubles = 0, rates_work_cap = 0;      // cap 0: the default of include/lsx_hip_rates.h
-    // ... of lsx_hip_radiative_losses (lsx_losses.hip), with the weights of a call (losses_wnu: the trapezoid rule in frequency over
-    // the merged grid, the default)
-    double *d_losses_work = nullptr, *d_losses_wnu = nullptr;
+    // the work arrays and the per-call tables of the final passes, by lsxd::FinalBuf (above: what each holds)
+    lsxd::GrowBuf buf[lsxd::BUF_COUNT];
+    // the weights of a call of lsx_hip_radiative_losses (losses_wnu: the trapezoid rule in frequency over the merged grid, the default)
+    double* d_losses_wnu = nullptr;
     std::vector<double> losses_wnu;
-    size_t losses_work_doubles = 0, losses_work_cap = 0;    // cap 0: the default of include/lsx_hip_losses.h
-    // ... of lsx_hip_depth_rays (lsx_depth.hip)
-    double* d_depth_work = nullptr;
-    size_t depth_work_doubles = 0, depth_work_cap = 0;      // cap 0: the default of include/lsx_hip_depth.h
-    // ... and of lsx_hip_spectrum (lsx_spectrum.hip): the tables of a call (they depend on the call's wavelengths: rebuilt per call,
-    // the buffer grows as needed) and the arrays of a pass (allocated at first use, under spec_work_cap bytes)
-    char* d_spec_tab = nullptr;
-    size_t spec_tab_bytes = 0;
-    double* d_spec_work = nullptr;
-    size_t spec_work_doubles = 0, spec_work_cap = 0;        // cap 0: the default of include/lsx_hip_spectrum.h
-    // ... and of lsx_hip_stokes_rays (lsx_stokes.hip): the Zeeman pattern tables of a call (rebuilt per call, the buffer grows as
-    // needed) and the angles, the field and the result of a pass (allocated at first use, under stokes_work_cap bytes)
-    char* d_stokes_tab = nullptr;
-    size_t stokes_tab_bytes = 0;
-    double* d_stokes_work = nullptr;
-    size_t stokes_work_doubles = 0, stokes_work_cap = 0;    // cap 0: the default of include/lsx_hip_stokes.h
-    // ... and of lsx_hip_response_stokes (lsx_stokes_response.hip): pattern tables and requested depths of a call, and the arrays of
-    // a pass (angles, field, nodes, kept states, the two results)
-    char* d_stresp_tab = nullptr;
-    size_t stresp_tab_bytes = 0;
-    double* d_stresp_work = nullptr;
-    size_t stresp_work_doubles = 0, stresp_work_cap = 0;    // cap 0: the default of include/lsx_hip_stokes_response.h
-    // ... and of the field fit (lsx_fit.hip, include/lsx_hip_fit.h): basis, observation, weights, the kept Stokes vectors, the Jacobian
-    // and the sums of a group of columns, under fit_work_cap bytes
-    double* d_fit_work = nullptr;
-    size_t fit_work_doubles = 0, fit_work_cap = 0;          // cap 0: the default of include/lsx_hip_fit.h
     // Ng acceleration of the populations (lsx_ng.hip, include/lsx_hip_ng.h): off (order 0) unless lsx_hip_ng_configure turns it on
     int ng_order = 0, ng_delay = 0;
     double* d_ng_hist = nullptr;         // [col][order + 2][NLtot][k]: the stored populations, slot = the column's counter
@@ -250,6 +274,39 @@ int dmalloc(T** p, size_t count)
     hipError_t e = hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T));
     if (e != hipSuccess) return fail(LSX_EDEVICE, "hipMalloc(%zu bytes): %s", count * sizeof(T), hipGetErrorString(e));
     return LSX_OK;
+}
+
+inline int GrowBuf::reserve(lsx_ctx* c, size_t nbytes)
+{
+    if (bytes >= nbytes) return LSX_OK;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (p) HIPCHK(hipFree(p));
+    p = nullptr;
+    bytes = 0;
+    const int rc = dmalloc(&p, nbytes);
+    if (rc) return rc;
+    bytes = nbytes;
+    return LSX_OK;
+}
+
+inline int GrowBuf::set_cap(lsx_ctx* c, FinalBuf b, const char* who, size_t nbytes)
+{
+    if (!c) return fail(LSX_EINVAL, "%s: null context", who);
+    GrowBuf& w = c->buf[b];
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (w.p) HIPCHK(hipFree(w.p));
+    w.p = nullptr;
+    w.bytes = 0;
+    w.cap = nbytes;
+    return LSX_OK;
+}
+
+inline void GrowBuf::release()
+{
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    bytes = 0;
 }
 
 template <typename T>

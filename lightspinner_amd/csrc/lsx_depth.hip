@@ -230,14 +230,7 @@ void launch_chunk(const DepthParams& p, bool par, dim3 grid, hipStream_t st)
 
 extern "C" int lsx_hip_depth_rays_work_cap(lsx_ctx* c, size_t nbytes)
 {
-    if (!c) return fail(LSX_EINVAL, "lsx_hip_depth_rays_work_cap: null context");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (c->d_depth_work) HIPCHK(hipFree(c->d_depth_work));       // the next call allocates under the new cap
-    c->d_depth_work = nullptr;
-    c->depth_work_doubles = 0;
-    c->depth_work_cap = nbytes;
-    return LSX_OK;
+    return GrowBuf::set_cap(c, BUF_DEPTH_WORK, "lsx_hip_depth_rays_work_cap", nbytes);
 }
 
 extern "C" int lsx_hip_depth_rays(lsx_ctx* c, int32_t nmu, const double* mu, int32_t col0, int32_t ncol, int32_t la0, int32_t nla,
@@ -250,9 +243,7 @@ extern "C" int lsx_hip_depth_rays(lsx_ctx* c, int32_t nmu, const double* mu, int
     int rc = final_check_angles("lsx_hip_depth_rays", nmu, mu);
     if (!rc) rc = final_check_range(c, "lsx_hip_depth_rays", col0, ncol);
     if (rc) return rc;
-    if (nla < 1) return fail(LSX_EINVAL, "lsx_hip_depth_rays: nla = %d, need at least one wavelength", (int)nla);
-    if (la0 < 0 || (int64_t)la0 + nla > c->Nspect)
-        return fail(LSX_EINVAL, "lsx_hip_depth_rays: wavelengths [%d, %d) are outside the grid's %d", (int)la0, (int)la0 + (int)nla, c->Nspect);
+    if ((rc = final_check_window(c, "lsx_hip_depth_rays", la0, nla))) return rc;
     const size_t zper = (size_t)nmu * nla;                       // doubles of z_tau1 per column
     const size_t per = zper * c->Nspace;                         // ... of each of the five depth-resolved arrays
     if ((chi || S || tau || I || contrib) && nbytes_each != (size_t)ncol * per * 8)
@@ -264,40 +255,24 @@ extern "C" int lsx_hip_depth_rays(lsx_ctx* c, int32_t nmu, const double* mu, int
     if ((rc = final_tables(c, "lsx_hip_depth_rays"))) return rc;
 
     // columns per pass: the arrays of a pass stay under the cap (one column's need if that alone is more)
+    GrowBuf& work = c->buf[BUF_DEPTH_WORK];
     const size_t wcol = 5 * per + zper;
-    const size_t cap = c->depth_work_cap ? c->depth_work_cap : kWorkCapDefault;
-    const size_t chunk = std::max<size_t>(1, std::min<size_t>(std::min<size_t>(ncol, 65535), cap / (wcol * 8)));     // (and a grid's y limit)
-    const size_t need = chunk * wcol;
-    if (c->depth_work_doubles < need) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->d_depth_work) HIPCHK(hipFree(c->d_depth_work));
-        c->d_depth_work = nullptr;
-        c->depth_work_doubles = 0;
-        if ((rc = dmalloc(&c->d_depth_work, need))) return rc;
-        c->depth_work_doubles = need;
-    }
+    const size_t chunk = pass_columns(ncol, work.cap, kWorkCapDefault, wcol, kGridYLimit);
+    if ((rc = work.reserve(c, chunk * wcol * 8))) return rc;
     if ((rc = ensure_stage(c, (size_t)nmu))) return rc;          // the angles go through the staging buffer
     double* d_mu = c->d_stage;
     HIPCHK(hipMemcpyAsync(d_mu, mu, (size_t)nmu * 8, hipMemcpyHostToDevice, c->stream));
 
     DepthParams p{};
-    p.Ns = c->Nspace; p.Nspect = c->Nspect; p.NLtot = c->NLtot; p.Natoms = c->Natoms; p.NlinesA = std::max(1, c->Nlines);
-    p.Ncont = c->Ncont; p.L = c->L; p.Nrays = c->Nrays; p.nmu = nmu; p.la0 = la0; p.nla = nla;
-    p.phi_compact = c->phi_compact; p.sca_per_lambda = c->sca_per_lambda; p.phi_G = c->phi_group;
-    p.til_col = (int64_t)c->til_col; p.phi_col = (int64_t)c->phi_col; p.sca_col = (int64_t)c->sca_col;
-    p.wavelength = c->d_wavelength; p.u_la = c->d_u_la; p.exp2_tab = c->d_exp2_tab; p.voigt_W = c->d_voigt_w; p.mu = d_mu;
-    p.la_ptr = c->d_final_ptr; p.ents = c->d_final_ent; p.la_tile = c->d_final_tile;
-    p.height = c->d_height; p.temperature = c->d_temperature; p.n = c->d_n; p.nsr = c->d_nsr;
-    p.bnd = c->d_bnd;
-    p.bgchi_T = c->d_bgchi; p.bgeta_T = c->d_bgeta; p.J_T = c->d_J[c->jcur];      // what lsx_get(LSX_J) returns at this moment
-    p.E_T = c->d_E; p.sca = c->d_sca; p.phi_T = c->d_phi;
-    p.aDamp = c->d_aDamp; p.vBroad = c->d_vBroad; p.vlos = c->d_vlos; p.prof_kind = c->d_prof_kind;
+    final_fill(p, c);
+    final_fill_angles(p, c);
+    p.nmu = nmu; p.la0 = la0; p.nla = nla; p.mu = d_mu;
     const bool par = c->solver == LSX_SOLVER_PARABOLIC;
 
     for (size_t b0 = 0; b0 < (size_t)ncol; b0 += chunk) {
         const size_t nb = std::min(chunk, (size_t)ncol - b0);
         p.col0 = (int32_t)(col0 + b0);
-        double* w = c->d_depth_work;
+        double* w = work.as<double>();
         p.chi = w; p.S = w + nb * per; p.tau = w + 2 * nb * per; p.I = w + 3 * nb * per; p.contrib = w + 4 * nb * per;
         p.ztau1 = w + 5 * nb * per;
         const dim3 grid((unsigned)((nla + 63) / 64), (unsigned)nb);

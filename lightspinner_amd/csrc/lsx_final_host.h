@@ -1,6 +1,8 @@
-// lsx_final_host.h -- host side of what the final passes share: the argument rules of their entry points and the
-// column-independent tables of the context's own grid (lsx_rays.hip, lsx_rates.hip, lsx_losses.hip, lsx_depth.hip; lsx_spectrum.hip
-// takes the argument rules only: its tables depend on the call's wavelengths).  `who` is the entry point's name in the messages.
+// lsx_final_host.h -- host side of what the final passes share: the argument rules of their entry points, the
+// column-independent tables of the context's own grid and the fill of the kernel parameters that name them (lsx_rays.hip,
+// lsx_rates.hip, lsx_losses.hip, lsx_depth.hip, lsx_stokes.hip, lsx_stokes_response.hip; lsx_spectrum.hip takes the argument rules and
+// final_fill_angles only: its tables depend on the call's wavelengths).  `who` is the entry point's name in the messages.  The buffers
+// of the passes (GrowBuf), the description of a Stokes call and what the Stokes units share: lsx_ctx.h; the columns of a pass: lsx_plan.h.
 #pragma once
 #include <algorithm>
 #include <vector>
@@ -24,6 +26,15 @@ inline int final_check_range(const lsx_ctx* c, const char* who, int32_t col0, in
 {
     if (col0 < 0 || ncol < 1 || (int64_t)col0 + ncol > c->ncol)
         return fail(LSX_EINVAL, "%s: columns [%d, %d) are outside the context's %d", who, (int)col0, (int)col0 + (int)ncol, c->ncol);
+    return LSX_OK;
+}
+
+// a call's window [la0, la0 + nla) of the merged wavelength grid
+inline int final_check_window(const lsx_ctx* c, const char* who, int32_t la0, int32_t nla)
+{
+    if (nla < 1) return fail(LSX_EINVAL, "%s: nla = %d, need at least one wavelength", who, (int)nla);
+    if (la0 < 0 || (int64_t)la0 + nla > c->Nspect)
+        return fail(LSX_EINVAL, "%s: wavelengths [%d, %d) are outside the grid's %d", who, (int)la0, (int)la0 + (int)nla, c->Nspect);
     return LSX_OK;
 }
 
@@ -109,6 +120,32 @@ inline int final_tables(lsx_ctx* c, const char* who)
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));                      // the host vectors go out of scope
     return LSX_OK;
+}
+
+// ---- the kernel parameters the passes share: the host side of final_column<P> and final_angles<P> (lsx_final_dev.h), which read
+// these fields by name from every unit's parameter struct.  What is a unit's own stays in the unit ----
+// what final_column and the tables need: dimensions, strides, the grid, the tables (final_tables has run), the state of the columns
+template <typename P>
+void final_fill(P& p, const lsx_ctx* c)
+{
+    p.Ns = c->Nspace; p.Nspect = c->Nspect; p.NLtot = c->NLtot; p.Ncont = c->Ncont; p.L = c->L; p.Nrays = c->Nrays;
+    p.phi_compact = c->phi_compact; p.sca_per_lambda = c->sca_per_lambda; p.phi_G = c->phi_group;
+    p.til_col = (int64_t)c->til_col; p.phi_col = (int64_t)c->phi_col; p.sca_col = (int64_t)c->sca_col;
+    p.wavelength = c->d_wavelength; p.u_la = c->d_u_la; p.exp2_tab = c->d_exp2_tab;
+    p.la_ptr = c->d_final_ptr; p.ents = c->d_final_ent; p.la_tile = c->d_final_tile;
+    p.height = c->d_height; p.temperature = c->d_temperature; p.n = c->d_n; p.nsr = c->d_nsr;
+    p.bgchi_T = c->d_bgchi; p.bgeta_T = c->d_bgeta; p.J_T = c->d_J[c->jcur];      // what lsx_get(LSX_J) returns at this moment
+    p.E_T = c->d_E; p.sca = c->d_sca; p.phi_T = c->d_phi;
+    p.bnd = c->d_bnd;
+}
+
+// what final_angles needs: the kept broadening arrays, from which a profile is formed at another angle or wavelength
+template <typename P>
+void final_fill_angles(P& p, const lsx_ctx* c)
+{
+    p.Natoms = c->Natoms; p.NlinesA = std::max(1, c->Nlines);
+    p.voigt_W = c->d_voigt_w;
+    p.aDamp = c->d_aDamp; p.vBroad = c->d_vBroad; p.vlos = c->d_vlos; p.prof_kind = c->d_prof_kind;
 }
 
 } // namespace lsxd

@@ -126,19 +126,6 @@ __global__ void __launch_bounds__(64) k_fit_step(const StepParams p)
     p.status[c] = st;
 }
 
-int fit_reserve(lsx_ctx* c, size_t need)
-{
-    if (c->fit_work_doubles >= need) return LSX_OK;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (c->d_fit_work) HIPCHK(hipFree(c->d_fit_work));
-    c->d_fit_work = nullptr;
-    c->fit_work_doubles = 0;
-    const int rc = dmalloc(&c->d_fit_work, need);
-    if (rc) return rc;
-    c->fit_work_doubles = need;
-    return LSX_OK;
-}
-
 bool all_finite(const double* a, size_t n, size_t& bad)
 {
     for (size_t i = 0; i < n; ++i)
@@ -201,10 +188,8 @@ int fit_run(lsx_ctx* c, const char* who, bool normal, int32_t nmu, const double*
         return fail(LSX_EINVAL, "%s: null argument", who);
     int rc = final_check_angles(who, nmu, mu);
     if (!rc) rc = final_check_range(c, who, col0, ncol);
+    if (!rc) rc = final_check_window(c, who, la0, nla);
     if (rc) return rc;
-    if (nla < 1) return fail(LSX_EINVAL, "%s: nla = %d, need at least one wavelength", who, (int)nla);
-    if (la0 < 0 || (int64_t)la0 + nla > c->Nspect)
-        return fail(LSX_EINVAL, "%s: wavelengths [%d, %d) are outside the grid's %d", who, (int)la0, (int)la0 + (int)nla, c->Nspect);
     int64_t Psum = 0;
     for (int a = 0; a < 3; ++a) {
         if (nnode[a] < 0) return fail(LSX_EINVAL, "%s: nnode[%d] = %d is negative", who, a, (int)nnode[a]);
@@ -241,11 +226,14 @@ int fit_run(lsx_ctx* c, const char* who, bool normal, int32_t nmu, const double*
                                                   basis + (size_t)row0[a] * Ns, (size_t)Ns, (size_t)k);
     uint32_t params = 0;
     for (int a = 0; a < 3; ++a) params |= nnode[a] > 0 ? 1u << a : 0u;
+    // what the passes are asked for columns [g0, g0 + ng) of the fit's
+    const auto call = [&](size_t g0, size_t ng) {
+        return StokesCall{nmu, mu, col0 + (int32_t)g0, (int32_t)ng, la0, nla, F[0] + g0 * Ns, F[1] + g0 * Ns, F[2] + g0 * Ns,
+                          ncomp, alpha, strength, shift};
+    };
     // chi2 alone: the response's rules without an amplitude's (the Stokes pass's rules are their first part, in its order)
     static const double unit_amp[3] = {0.0, 1.0, 1.0};
-    if ((rc = response_stokes_check(c, who, nmu, mu, col0, ncol, la0, nla, F[0], F[1], F[2], ncomp, alpha, strength, shift,
-                                    normal ? params : 2u, normal ? amplitude : unit_amp, 0, nullptr)))
-        return rc;
+    if ((rc = response_stokes_check(c, who, call(0, NC), normal ? params : 2u, normal ? amplitude : unit_amp, 0, nullptr))) return rc;
     if (field_out)
         for (size_t q = 0; q < NC; ++q)
             for (int a = 0; a < 3; ++a) std::copy(F[a] + q * Ns, F[a] + (q + 1) * Ns, field_out + (q * 3 + a) * Ns);
@@ -256,10 +244,10 @@ int fit_run(lsx_ctx* c, const char* who, bool normal, int32_t nmu, const double*
     const size_t sums = 1 + (normal ? (size_t)P + (size_t)P * P : 0);
     const size_t wcol = (2 + nW) * M + 2 * M + (normal ? (size_t)P * M : 0) + sums;      // obs, S, weight; R, W; J; the sums
     const size_t head = (size_t)P * Ns;
-    const size_t cap = c->fit_work_cap ? c->fit_work_cap : kWorkCapDefault;
-    const size_t G = std::max<size_t>(1, std::min<size_t>(std::min<size_t>(NC, 65535), cap / (wcol * 8)));
-    if ((rc = fit_reserve(c, head + G * wcol))) return rc;
-    double* d_basis = c->d_fit_work;
+    GrowBuf& work = c->buf[BUF_FIT_WORK];
+    const size_t G = pass_columns(NC, work.cap, kWorkCapDefault, wcol, kGridYLimit);
+    if ((rc = work.reserve(c, (head + G * wcol) * 8))) return rc;
+    double* d_basis = work.as<double>();
     double* d_obs = d_basis + head;
     double* d_S = d_obs + G * M;
     double* d_wt = d_S + G * M;
@@ -284,18 +272,14 @@ int fit_run(lsx_ctx* c, const char* who, bool normal, int32_t nmu, const double*
         const size_t ng = std::min(G, NC - g0);
         HIPCHK(hipMemcpyAsync(d_obs, obs + g0 * M, ng * M * 8, hipMemcpyHostToDevice, c->stream));
         if (weight) HIPCHK(hipMemcpyAsync(d_wt, weight + g0 * M, ng * M * 8, hipMemcpyHostToDevice, c->stream));
+        const StokesCall s = call(g0, ng);
         KeepStokes keep;
         keep.c = c; keep.d_S = d_S; keep.M = M;
-        if ((rc = stokes_rays_run(c, who, nmu, mu, col0 + (int32_t)g0, (int32_t)ng, la0, nla, F[0] + g0 * Ns, F[1] + g0 * Ns, F[2] + g0 * Ns,
-                                  ncomp, alpha, strength, shift, nullptr, 0, &keep)))
-            return rc;
+        if ((rc = stokes_rays_run(c, who, s, nullptr, 0, &keep))) return rc;
         if (normal) {
             SumPass sum;
             sum.c = c; sum.p = p;
-            if ((rc = response_stokes_run(c, who, nmu, mu, col0 + (int32_t)g0, (int32_t)ng, la0, nla, F[0] + g0 * Ns, F[1] + g0 * Ns,
-                                          F[2] + g0 * Ns, ncomp, alpha, strength, shift, params, amplitude, 0, nullptr, nullptr, 0, nullptr,
-                                          &sum)))
-                return rc;
+            if ((rc = response_stokes_run(c, who, s, params, amplitude, 0, nullptr, nullptr, 0, nullptr, &sum))) return rc;
         } else {
             launch_sums(c, p, 0, ng, nullptr, false);
             HIPCHK(hipGetLastError());
@@ -314,14 +298,7 @@ int fit_run(lsx_ctx* c, const char* who, bool normal, int32_t nmu, const double*
 
 extern "C" int lsx_hip_fit_field_work_cap(lsx_ctx* c, size_t nbytes)
 {
-    if (!c) return fail(LSX_EINVAL, "lsx_hip_fit_field_work_cap: null context");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (c->d_fit_work) HIPCHK(hipFree(c->d_fit_work));             // the next call allocates under the new cap
-    c->d_fit_work = nullptr;
-    c->fit_work_doubles = 0;
-    c->fit_work_cap = nbytes;
-    return LSX_OK;
+    return GrowBuf::set_cap(c, BUF_FIT_WORK, "lsx_hip_fit_field_work_cap", nbytes);
 }
 
 extern "C" int lsx_hip_fit_field_normal(lsx_ctx* c, int32_t nmu, const double* mu, int32_t col0, int32_t ncol, int32_t la0, int32_t nla,
@@ -360,11 +337,11 @@ extern "C" int lsx_hip_fit_field_step(lsx_ctx* c, int32_t ncol, int32_t P, const
     HIPCHK(hipSetDevice(c->device));
     // per column: hess, grad, nodes, trial, lambda, predicted, status (a double's place)
     const size_t PP = (size_t)P * P, wcol = PP + 3 * (size_t)P + 3, head = 2 * (size_t)P;
-    const size_t cap = c->fit_work_cap ? c->fit_work_cap : kWorkCapDefault;
-    const size_t G = std::max<size_t>(1, std::min<size_t>((size_t)ncol, cap / (wcol * 8)));
-    int rc = fit_reserve(c, head + G * wcol);
+    GrowBuf& work = c->buf[BUF_FIT_WORK];
+    const size_t G = pass_columns((size_t)ncol, work.cap, kWorkCapDefault, wcol, kNoColumnLimit);      // (the columns are the grid's x)
+    const int rc = work.reserve(c, (head + G * wcol) * 8);
     if (rc) return rc;
-    double* d_lo = c->d_fit_work;
+    double* d_lo = work.as<double>();
     double* d_hi = d_lo + P;
     double* d_hess = d_hi + P;
     double* d_grad = d_hess + G * PP;

@@ -1277,10 +1277,10 @@ void lsx_destroy(lsx_ctx* c)
                     c->d_res, c->d_stage, c->d_debug, c->d_colmask, c->d_bgxchi, c->d_bgxeta, c->d_Psi2, c->d_fast_tiles, c->d_fast_rest, c->d_nsr, c->d_cont_li, c->d_cont_lj, c->d_exp2_tab, c->d_voigt_w, c->d_muz, c->d_wmu, c->d_optab, c->d_trans_row, c->d_fgtab, c->d_level_atom,
                     c->d_sa_atoms, c->d_sa_lines, c->d_sa_colls, c->d_sa_spl, c->d_sa_levE, c->d_sa_levg, c->d_sa_levnD, c->d_sa_levdZ,
                     c->d_vBroad, c->d_aDamp, c->d_vlos, c->d_prof_kind, c->d_final_ptr, c->d_final_tile, c->d_final_row, c->d_final_ent,
-                    c->d_rates_work, c->d_losses_work, c->d_losses_wnu, c->d_depth_work, c->d_spec_tab, c->d_spec_work,
-                    c->d_stokes_tab, c->d_stokes_work, c->d_stresp_tab, c->d_stresp_work, c->d_fit_work};
+                    c->d_losses_wnu};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
+    for (GrowBuf& b : c->buf) b.release();
     for (int v = 0; v < LSX_FGC_LISTS; ++v) if (c->d_fast_cols[v]) (void)hipFree(c->d_fast_cols[v]);
     for (auto& k : c->classes) {
         if (k.d_tiles) (void)hipFree(k.d_tiles);

@@ -310,14 +310,7 @@ size_t work_doubles_per_column(const lsx_ctx* c) { return (size_t)c->Nspace * (3
 
 extern "C" int lsx_hip_radiative_losses_work_cap(lsx_ctx* c, size_t nbytes)
 {
-    if (!c) return fail(LSX_EINVAL, "lsx_hip_radiative_losses_work_cap: null context");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (c->d_losses_work) HIPCHK(hipFree(c->d_losses_work));     // the next call allocates under the new cap
-    c->d_losses_work = nullptr;
-    c->losses_work_doubles = 0;
-    c->losses_work_cap = nbytes;
-    return LSX_OK;
+    return GrowBuf::set_cap(c, BUF_LOSSES_WORK, "lsx_hip_radiative_losses_work_cap", nbytes);
 }
 
 extern "C" int lsx_hip_radiative_losses(lsx_ctx* c, int32_t col0, int32_t ncol, const double* wnu, double* F, double* Q, double* Qt,
@@ -347,36 +340,21 @@ extern "C" int lsx_hip_radiative_losses(lsx_ctx* c, int32_t col0, int32_t ncol, 
     }
 
     // columns per pass: the work arrays stay under the cap (one column's need if that alone is more; a grid's y limit)
+    GrowBuf& work = c->buf[BUF_LOSSES_WORK];
     const size_t wcol = work_doubles_per_column(c);
-    const size_t cap = c->losses_work_cap ? c->losses_work_cap : kWorkCapDefault;
-    const size_t chunk = std::max<size_t>(1, std::min<size_t>(std::min<size_t>(ncol, 65535), cap / (wcol * 8)));
-    const size_t need = chunk * wcol + 2;                        // (+ 2: the pairs start on a 16-byte boundary)
-    if (c->losses_work_doubles < need) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->d_losses_work) HIPCHK(hipFree(c->d_losses_work));
-        c->d_losses_work = nullptr;
-        c->losses_work_doubles = 0;
-        if ((rc = dmalloc(&c->d_losses_work, need))) return rc;
-        c->losses_work_doubles = need;
-    }
+    const size_t chunk = pass_columns(ncol, work.cap, kWorkCapDefault, wcol, kGridYLimit);
+    if ((rc = work.reserve(c, (chunk * wcol + 2) * 8))) return rc;       // (+ 2: the pairs start on a 16-byte boundary)
     // the results of a chunk leave through the staging buffer: F, Q, Qt, and H / D in the entry's layout where asked for
     const size_t stage_need = chunk * (2 * Ns + per_t + (H ? per_m : 0) + (D ? per_m : 0));
     if ((rc = ensure_stage(c, stage_need))) return rc;
     HIPCHK(hipMemcpyAsync(c->d_losses_wnu, wnu ? wnu : c->losses_wnu.data(), Nspect * 8, hipMemcpyHostToDevice, c->stream));
 
     LossParams p{};
-    p.Ns = c->Nspace; p.Nspect = c->Nspect; p.NLtot = c->NLtot; p.Ncont = c->Ncont; p.L = c->L; p.Nrays = c->Nrays;
+    final_fill(p, c);
     p.SNl = c->SNl; p.Ntrans = c->Ntrans; p.Nlines = c->Nlines;
-    p.phi_compact = c->phi_compact; p.sca_per_lambda = c->sca_per_lambda; p.phi_G = c->phi_group;
-    p.til_col = (int64_t)c->til_col; p.phi_col = (int64_t)c->phi_col; p.sca_col = (int64_t)c->sca_col;
-    p.wavelength = c->d_wavelength; p.u_la = c->d_u_la; p.exp2_tab = c->d_exp2_tab; p.zmu = c->d_zmu; p.muz = c->d_muz; p.wmuh = c->d_wmuh;
-    p.wl = c->d_wl; p.alpha = c->d_alpha; p.wnu = c->d_losses_wnu;
-    p.la_ptr = c->d_final_ptr; p.ents = c->d_final_ent; p.la_tile = c->d_final_tile;
+    p.zmu = c->d_zmu; p.muz = c->d_muz; p.wmuh = c->d_wmuh; p.wl = c->d_wl; p.alpha = c->d_alpha; p.wnu = c->d_losses_wnu;
     p.trans = c->d_trans; p.trans_row = c->d_final_row; p.active = c->d_active;
-    p.height = c->d_height; p.temperature = c->d_temperature; p.n = c->d_n; p.nsr = c->d_nsr; p.wphi = c->d_wphi;
-    p.bgchi_T = c->d_bgchi; p.bgeta_T = c->d_bgeta; p.J_T = c->d_J[c->jcur];      // what lsx_get(LSX_J) returns at this moment
-    p.E_T = c->d_E; p.sca = c->d_sca; p.phi_T = c->d_phi;
-    p.bnd = c->d_bnd;
+    p.wphi = c->d_wphi;
     p.wsum = 0.0;
     for (int dir = 0; dir < 2; ++dir)
         for (int m = 0; m < c->Nrays; ++m) p.wsum += c->wmuh[m];
@@ -387,10 +365,10 @@ extern "C" int lsx_hip_radiative_losses(lsx_ctx* c, int32_t col0, int32_t ncol, 
         const size_t nb = std::min(chunk, (size_t)ncol - b0);
         p.col0 = (int32_t)(col0 + b0);
         p.ncols = (int32_t)nb;
-        p.Hw = c->d_losses_work;
+        p.Hw = work.as<double>();
         p.Dw = p.Hw + nb * per_m;
         p.Jp = p.Dw + nb * per_m;
-        p.PP = reinterpret_cast<double2*>(c->d_losses_work + ((3 * nb * per_m + 1) & ~(size_t)1));
+        p.PP = reinterpret_cast<double2*>(p.Hw + ((3 * nb * per_m + 1) & ~(size_t)1));
         double* st = c->d_stage;
         p.F = st; st += nb * Ns;
         p.Q = st; st += nb * Ns;

@@ -369,4 +369,16 @@ inline int fgc_lines(int v) { return kLkLines[v & 3]; }
 // LDS of a workgroup of NW waves of the column-mapped epilogue: tables for MAXF continua, NW x (3 + lines) streams of LSX_FGC_ROWS rows
 inline size_t fgc_lds_bytes(int L, int maxf, int nw, int lines) { return ((size_t)2 * maxf * L + (size_t)3 * L + (size_t)nw * (3 + lines) * LSX_FGC_ROWS * L) * sizeof(double); }
 
+// Columns per pass of a final pass: as many of the call's ncol as keep the pass's work arrays, doubles_per_column
+// doubles a column, under cap_bytes (0: the unit's default_bytes), at most `limit` (a grid's y) and at least one: one column's need
+// is allocated even if that alone is above the cap
+constexpr size_t kGridYLimit = 65535, kNoColumnLimit = ~(size_t)0;
+inline size_t pass_columns(size_t ncol, size_t cap_bytes, size_t default_bytes, size_t doubles_per_column, size_t limit)
+{
+    const size_t fit = (cap_bytes ? cap_bytes : default_bytes) / (8 * doubles_per_column);
+    const size_t most = ncol < limit ? ncol : limit;
+    const size_t n = most < fit ? most : fit;
+    return n > 1 ? n : 1;
+}
+
 } // namespace lsxd

@@ -289,6 +289,12 @@ int32_t lsx_plan_rs_classes(const lsx_problem* d, int32_t* out, int32_t max)
     return n;
 }
 
+// the columns-per-pass rule of the final passes (lsx_plan.h, pass_columns) as their entries call it; tests/test_host_logic.py
+uint64_t lsx_plan_pass_columns(uint64_t ncol, uint64_t cap_bytes, uint64_t default_bytes, uint64_t doubles_per_column, uint64_t limit)
+{
+    return pass_columns((size_t)ncol, (size_t)cap_bytes, (size_t)default_bytes, (size_t)doubles_per_column, (size_t)limit);
+}
+
 } // extern "C"
 
 // what lsx_grid.cpp expects from the runtime (the product defines these in lsx_hip.hip)

@@ -261,14 +261,7 @@ size_t work_doubles_per_column(const lsx_ctx* c) { return (size_t)c->Nspace * ((
 
 extern "C" int lsx_hip_radiative_rates_work_cap(lsx_ctx* c, size_t nbytes)
 {
-    if (!c) return fail(LSX_EINVAL, "lsx_hip_radiative_rates_work_cap: null context");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (c->d_rates_work) HIPCHK(hipFree(c->d_rates_work));       // the next call allocates under the new cap
-    c->d_rates_work = nullptr;
-    c->rates_work_doubles = 0;
-    c->rates_work_cap = nbytes;
-    return LSX_OK;
+    return GrowBuf::set_cap(c, BUF_RATES_WORK, "lsx_hip_radiative_rates_work_cap", nbytes);
 }
 
 extern "C" int lsx_hip_radiative_rates(lsx_ctx* c, int32_t col0, int32_t ncol, double* Rij, double* Rji, double* Rji_ref, size_t nbytes_each)
@@ -287,33 +280,19 @@ extern "C" int lsx_hip_radiative_rates(lsx_ctx* c, int32_t col0, int32_t ncol, d
     if ((rc = final_tables(c, "lsx_hip_radiative_rates"))) return rc;
 
     // columns per pass: the work arrays stay under the cap (one column's need if that alone is more)
+    // (no limit: the pass's grid has the columns in its y like the other passes', whose 65535 this entry has never honoured)
+    GrowBuf& work = c->buf[BUF_RATES_WORK];
     const size_t wcol = work_doubles_per_column(c);
-    const size_t cap = c->rates_work_cap ? c->rates_work_cap : kWorkCapDefault;
-    const size_t chunk = std::max<size_t>(1, std::min<size_t>(ncol, cap / (wcol * 8)));
-    const size_t need = chunk * wcol + 2;                        // (+ 2: the pairs start on a 16-byte boundary)
-    if (c->rates_work_doubles < need) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->d_rates_work) HIPCHK(hipFree(c->d_rates_work));
-        c->d_rates_work = nullptr;
-        c->rates_work_doubles = 0;
-        if ((rc = dmalloc(&c->d_rates_work, need))) return rc;
-        c->rates_work_doubles = need;
-    }
+    const size_t chunk = pass_columns(ncol, work.cap, kWorkCapDefault, wcol, kNoColumnLimit);
+    if ((rc = work.reserve(c, (chunk * wcol + 2) * 8))) return rc;       // (+ 2: the pairs start on a 16-byte boundary)
     if ((rc = ensure_stage(c, 3 * chunk * per))) return rc;      // the three results of a chunk leave through the staging buffer
 
     RatesParams p{};
-    p.Ns = c->Nspace; p.Nspect = c->Nspect; p.NLtot = c->NLtot; p.Ncont = c->Ncont; p.L = c->L; p.Nrays = c->Nrays;
+    final_fill(p, c);
     p.SNl = c->SNl; p.Ntrans = c->Ntrans; p.Nlines = c->Nlines;
-    p.phi_compact = c->phi_compact; p.sca_per_lambda = c->sca_per_lambda; p.phi_G = c->phi_group;
-    p.til_col = (int64_t)c->til_col; p.phi_col = (int64_t)c->phi_col; p.sca_col = (int64_t)c->sca_col;
-    p.wavelength = c->d_wavelength; p.u_la = c->d_u_la; p.exp2_tab = c->d_exp2_tab; p.zmu = c->d_zmu; p.wmuh = c->d_wmuh;
-    p.wl = c->d_wl; p.alpha = c->d_alpha;
-    p.la_ptr = c->d_final_ptr; p.ents = c->d_final_ent; p.la_tile = c->d_final_tile;
+    p.zmu = c->d_zmu; p.wmuh = c->d_wmuh; p.wl = c->d_wl; p.alpha = c->d_alpha;
     p.trans = c->d_trans; p.trans_row = c->d_final_row; p.active = c->d_active;
-    p.height = c->d_height; p.temperature = c->d_temperature; p.n = c->d_n; p.nsr = c->d_nsr; p.wphi = c->d_wphi;
-    p.bgchi_T = c->d_bgchi; p.bgeta_T = c->d_bgeta; p.J_T = c->d_J[c->jcur];      // what lsx_get(LSX_J) returns at this moment
-    p.E_T = c->d_E; p.sca = c->d_sca; p.phi_T = c->d_phi;
-    p.bnd = c->d_bnd;
+    p.wphi = c->d_wphi;
     p.wsum = 0.0;
     for (int dir = 0; dir < 2; ++dir)
         for (int m = 0; m < c->Nrays; ++m) p.wsum += c->wmuh[m];
@@ -324,8 +303,8 @@ extern "C" int lsx_hip_radiative_rates(lsx_ctx* c, int32_t col0, int32_t ncol, d
         const size_t nb = std::min(chunk, (size_t)ncol - b0);
         p.col0 = (int32_t)(col0 + b0);
         p.ncols = (int32_t)nb;
-        p.Jp = c->d_rates_work;
-        p.PP = reinterpret_cast<double2*>(c->d_rates_work + ((nb * (size_t)c->Nspace * c->Nspect + 1) & ~(size_t)1));
+        p.Jp = work.as<double>();
+        p.PP = reinterpret_cast<double2*>(p.Jp + ((nb * (size_t)c->Nspace * c->Nspect + 1) & ~(size_t)1));
         p.Rij = c->d_stage; p.Rji = c->d_stage + nb * per; p.Rji_ref = c->d_stage + 2 * nb * per;
         const dim3 grid((unsigned)((c->Nspect + 63) / 64), (unsigned)nb);
         for (int m0 = 0; m0 < c->Nrays;) {

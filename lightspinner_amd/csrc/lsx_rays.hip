@@ -169,17 +169,9 @@ extern "C" int lsx_hip_emergent_rays(lsx_ctx* c, int32_t nmu, const double* mu, 
     HIPCHK(hipMemcpyAsync(d_mu, mu, (size_t)nmu * 8, hipMemcpyHostToDevice, c->stream));
 
     RaysParams p{};
-    p.Ns = c->Nspace; p.Nspect = c->Nspect; p.NLtot = c->NLtot; p.Natoms = c->Natoms; p.NlinesA = std::max(1, c->Nlines);
-    p.Ncont = c->Ncont; p.L = c->L; p.Nrays = c->Nrays; p.nmu = nmu;
-    p.phi_compact = c->phi_compact; p.sca_per_lambda = c->sca_per_lambda; p.phi_G = c->phi_group;
-    p.til_col = (int64_t)c->til_col; p.phi_col = (int64_t)c->phi_col; p.sca_col = (int64_t)c->sca_col;
-    p.wavelength = c->d_wavelength; p.u_la = c->d_u_la; p.exp2_tab = c->d_exp2_tab; p.voigt_W = c->d_voigt_w; p.mu = d_mu;
-    p.la_ptr = c->d_final_ptr; p.ents = c->d_final_ent; p.la_tile = c->d_final_tile;
-    p.height = c->d_height; p.temperature = c->d_temperature; p.n = c->d_n; p.nsr = c->d_nsr;
-    p.bnd = c->d_bnd;
-    p.bgchi_T = c->d_bgchi; p.bgeta_T = c->d_bgeta; p.J_T = c->d_J[c->jcur];      // what lsx_get(LSX_J) returns at this moment
-    p.E_T = c->d_E; p.sca = c->d_sca; p.phi_T = c->d_phi;
-    p.aDamp = c->d_aDamp; p.vBroad = c->d_vBroad; p.vlos = c->d_vlos; p.prof_kind = c->d_prof_kind;
+    final_fill(p, c);
+    final_fill_angles(p, c);
+    p.nmu = nmu; p.mu = d_mu;
     p.out = d_out;
     const bool par = c->solver == LSX_SOLVER_PARABOLIC;
 

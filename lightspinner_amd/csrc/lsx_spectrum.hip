@@ -339,14 +339,7 @@ int spec_tables(const lsx_ctx* c, int nla, const double* w, const double* alpha,
 
 extern "C" int lsx_hip_spectrum_work_cap(lsx_ctx* c, size_t nbytes)
 {
-    if (!c) return fail(LSX_EINVAL, "lsx_hip_spectrum_work_cap: null context");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (c->d_spec_work) HIPCHK(hipFree(c->d_spec_work));         // the next call allocates under the new cap
-    c->d_spec_work = nullptr;
-    c->spec_work_doubles = 0;
-    c->spec_work_cap = nbytes;
-    return LSX_OK;
+    return GrowBuf::set_cap(c, BUF_SPEC_WORK, "lsx_hip_spectrum_work_cap", nbytes);
 }
 
 extern "C" int lsx_hip_spectrum(lsx_ctx* c, int32_t nla, const double* wavelength, const double* alpha, const double* bg_chi,
@@ -391,56 +384,42 @@ extern "C" int lsx_hip_spectrum(lsx_ctx* c, int32_t nla, const double* wavelengt
     const size_t a_wav = put(buf, wv), a_ula = put(buf, S.ula), a_t = put(buf, S.t), a_al = put(buf, S.ent_alpha), a_trd = put(buf, S.tr_d),
                  a_mu = put(buf, muv), a_o0 = put(buf, S.off0), a_o1 = put(buf, S.off1), a_ne = put(buf, S.blk_ne),
                  a_tid = put(buf, S.ent_tid), a_tri = put(buf, S.tr_i);
-    if (c->spec_tab_bytes < buf.size()) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->d_spec_tab) HIPCHK(hipFree(c->d_spec_tab));
-        c->d_spec_tab = nullptr;
-        c->spec_tab_bytes = 0;
-        if ((rc = dmalloc(&c->d_spec_tab, buf.size()))) return rc;
-        c->spec_tab_bytes = buf.size();
-    }
-    HIPCHK(hipMemcpyAsync(c->d_spec_tab, buf.data(), buf.size(), hipMemcpyHostToDevice, c->stream));
+    GrowBuf& tab = c->buf[BUF_SPEC_TAB];
+    if ((rc = tab.reserve(c, buf.size()))) return rc;
+    HIPCHK(hipMemcpyAsync(tab.p, buf.data(), buf.size(), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));                     // (the host buffer may go out of scope on any return below)
 
     // ---- columns per pass: the pass's arrays stay under the cap (one column's need if that alone is more) ----
     const size_t mat = (size_t)nla * c->Nspace;                  // one background array of a column
     const size_t nstream = xbg ? (want_sca ? 3 : 2) : 0;
     const size_t wcol = per + 2 * nstream * mat;                 // the result; the caller's arrays as they come and transposed
-    const size_t cap = c->spec_work_cap ? c->spec_work_cap : kWorkCapDefault;
-    const size_t chunk = std::max<size_t>(1, std::min<size_t>(std::min<size_t>(ncol, 65535), cap / (wcol * 8)));     // (and a grid's y limit)
-    const size_t need = chunk * wcol;
-    if (c->spec_work_doubles < need) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->d_spec_work) HIPCHK(hipFree(c->d_spec_work));
-        c->d_spec_work = nullptr;
-        c->spec_work_doubles = 0;
-        if ((rc = dmalloc(&c->d_spec_work, need))) return rc;
-        c->spec_work_doubles = need;
-    }
+    GrowBuf& work = c->buf[BUF_SPEC_WORK];
+    const size_t chunk = pass_columns(ncol, work.cap, kWorkCapDefault, wcol, kGridYLimit);
+    if ((rc = work.reserve(c, chunk * wcol * 8))) return rc;
 
     SpecParams p{};
-    p.Ns = c->Nspace; p.NLtot = c->NLtot; p.Natoms = c->Natoms; p.NlinesA = std::max(1, c->Nlines); p.Ncont = c->Ncont;
+    final_fill_angles(p, c);       // (final_fill is not for this unit: its tables are the call's, and SpecParams names no grid of the context)
+    p.Ns = c->Nspace; p.NLtot = c->NLtot; p.Ncont = c->Ncont;
     p.Ntrans = c->Ntrans; p.L = c->L; p.nmu = nmu; p.nla = nla; p.Emax = S.Emax;
     p.sca_per_lambda = c->sca_per_lambda; p.explicit_bg = xbg ? 1 : 0;
     p.til_col = (int64_t)c->til_col; p.sca_col = (int64_t)c->sca_col;
-    const char* tb = c->d_spec_tab;
+    const char* tb = tab.p;
     p.wav = (const double*)(tb + a_wav); p.ula = (const double*)(tb + a_ula); p.t = (const double*)(tb + a_t);
     p.ent_alpha = (const double*)(tb + a_al); p.tr_d = (const double*)(tb + a_trd); p.mu = (const double*)(tb + a_mu);
     p.off0 = (const int32_t*)(tb + a_o0); p.off1 = (const int32_t*)(tb + a_o1); p.blk_ne = (const int32_t*)(tb + a_ne);
     p.ent_tid = (const int32_t*)(tb + a_tid); p.tr_i = (const int32_t*)(tb + a_tri);
-    p.exp2_tab = c->d_exp2_tab; p.voigt_W = c->d_voigt_w;
+    p.exp2_tab = c->d_exp2_tab;
     p.height = c->d_height; p.temperature = c->d_temperature; p.n = c->d_n; p.nsr = c->d_nsr;
     p.bnd = c->d_bnd;
     p.bgchi_T = c->d_bgchi; p.bgeta_T = c->d_bgeta; p.J_T = c->d_J[c->jcur];      // what lsx_get(LSX_J) returns at this moment
     p.sca = c->d_sca;
-    p.aDamp = c->d_aDamp; p.vBroad = c->d_vBroad; p.vlos = c->d_vlos; p.prof_kind = c->d_prof_kind;
     const bool par = c->solver == LSX_SOLVER_PARABOLIC;
     const double* const src[3] = {bg_chi, bg_eta, bg_sca};
 
     for (size_t b0 = 0; b0 < (size_t)ncol; b0 += chunk) {
         const size_t nb = std::min(chunk, (size_t)ncol - b0);
         p.col0 = (int32_t)(col0 + b0);
-        double* wk = c->d_spec_work;
+        double* wk = work.as<double>();
         p.out = wk;
         double* raw = wk + nb * per;                              // [stream][nb][nla][Ns] as the caller has them
         double* tr = raw + nstream * nb * mat;                    // [stream][nb][Ns][nla]

@@ -183,122 +183,115 @@ void launch_chunk(const StokesParams& p, dim3 grid, size_t lds, hipStream_t st)
 
 extern "C" int lsx_hip_stokes_rays_work_cap(lsx_ctx* c, size_t nbytes)
 {
-    if (!c) return fail(LSX_EINVAL, "lsx_hip_stokes_rays_work_cap: null context");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (c->d_stokes_work) HIPCHK(hipFree(c->d_stokes_work));       // the next call allocates under the new cap
-    c->d_stokes_work = nullptr;
-    c->stokes_work_doubles = 0;
-    c->stokes_work_cap = nbytes;
+    return GrowBuf::set_cap(c, BUF_STOKES_WORK, "lsx_hip_stokes_rays_work_cap", nbytes);
+}
+
+// ---- what lsx_hip_stokes_rays shares with lsx_hip_response_stokes and the fit (declared in lsx_ctx.h) ----
+int lsxd::stokes_check_call(const lsx_ctx* c, const char* who, const StokesCall& s)
+{
+    if (!c || !s.mu || !s.B || !s.gammaB || !s.chiB) return fail(LSX_EINVAL, "%s: null argument", who);
+    if (c->Nlines && !s.ncomp) return fail(LSX_EINVAL, "%s: null ncomp (one count per line; zeros for no pattern)", who);
+    int rc = final_check_angles(who, s.nmu, s.mu);
+    if (!rc) rc = final_check_range(c, who, s.col0, s.ncol);
+    if (!rc) rc = final_check_window(c, who, s.la0, s.nla);
+    return rc;
+}
+
+int lsxd::stokes_check_state(const lsx_ctx* c, const char* who, const StokesCall& s)
+{
+    int rc;
+    std::string msg;
+    if ((rc = lsxst::check_field((size_t)s.ncol * c->Nspace, s.B, s.gammaB, s.chiB, msg))) return fail(rc, "%s: %s", who, msg.c_str());
+    if ((rc = lsxst::check_patterns(c->Nlines, s.ncomp, s.alpha, s.strength, s.shift, msg))) return fail(rc, "%s: %s", who, msg.c_str());
+    if ((rc = final_check_depths(c, who))) return rc;
+    if ((rc = final_check_columns(c, who, s.col0, s.ncol, FINAL_OTHER_ANGLE))) return rc;
+    // split profiles are formed from the kept broadening arrays, whether the context's own profiles depend on the ray or not
+    for (int q = s.col0; q < s.col0 + s.ncol && c->Nlines; ++q)
+        if (c->prof_kind.empty() || !c->prof_kind[q])
+            return fail(LSX_EUNSUPPORTED, "%s: the line profiles of column %d were handed over as arrays (lsx_set_columns): the library "
+                                          "cannot know them at another angle.  Build them with lsx_set_line_profiles or "
+                                          "lsx_set_atmosphere", who, q);
+    return LSX_OK;
+}
+
+int lsxd::stokes_patterns(const lsx_ctx* c, const char* who, const StokesCall& s, std::vector<int32_t>& pat_line, std::vector<double>& pat_tab)
+{
+    std::vector<uint8_t> wanted(std::max(1, c->Nlines), 0);
+    for (int t = 0; t < c->Ntrans; ++t) {
+        if (!c->htrans[t].is_line) continue;
+        const uint8_t* act = c->active.data() + (size_t)t * c->Nspect;
+        for (int la = s.la0; la < s.la0 + s.nla; ++la)
+            if (act[la]) { wanted[c->trans_row[t]] = 1; break; }
+    }
+    std::string msg;
+    const int rc = lsxst::pack_patterns(c->Nlines, s.ncomp, s.alpha, s.strength, s.shift, wanted, pat_line, pat_tab, msg);
+    return rc ? fail(rc, "%s: %s", who, msg.c_str()) : LSX_OK;
+}
+
+int lsxd::stokes_upload_field(lsx_ctx* c, const StokesCall& s, size_t b0, size_t nb, double* d_field)
+{
+    const size_t Ns = (size_t)c->Nspace;
+    const double* const src[3] = {s.B, s.gammaB, s.chiB};
+    for (int a = 0; a < 3; ++a)
+        HIPCHK(hipMemcpyAsync(d_field + (size_t)a * nb * Ns, src[a] + b0 * Ns, nb * Ns * 8, hipMemcpyHostToDevice, c->stream));
     return LSX_OK;
 }
 
 // The body of lsx_hip_stokes_rays.  sink null: the entry itself -- every pass is copied to out.  An internal caller (lsx_fit.hip) hands a
 // sink instead and out null: a pass's result stays in the pass's device array and the sink is called in the copy's place.
-int lsxd::stokes_rays_run(lsx_ctx* c, const char* who, int32_t nmu, const double* mu, int32_t col0, int32_t ncol, int32_t la0, int32_t nla,
-                          const double* B, const double* gammaB, const double* chiB,
-                          const int32_t* ncomp, const int32_t* alpha, const double* strength, const double* shift,
-                          double* out, size_t nbytes, PassSink* sink)
+int lsxd::stokes_rays_run(lsx_ctx* c, const char* who, const StokesCall& s, double* out, size_t nbytes, PassSink* sink)
 {
     // ---- everything is checked on the host before anything is launched ----
-    if (!c || !mu || !B || !gammaB || !chiB || (!out && !sink)) return fail(LSX_EINVAL, "%s: null argument", who);
-    if (c->Nlines && !ncomp) return fail(LSX_EINVAL, "%s: null ncomp (one count per line; zeros for no pattern)", who);
-    int rc = final_check_angles(who, nmu, mu);
-    if (!rc) rc = final_check_range(c, who, col0, ncol);
+    if (!out && !sink) return fail(LSX_EINVAL, "%s: null argument", who);
+    int rc = stokes_check_call(c, who, s);
     if (rc) return rc;
-    if (nla < 1) return fail(LSX_EINVAL, "%s: nla = %d, need at least one wavelength", who, (int)nla);
-    if (la0 < 0 || (int64_t)la0 + nla > c->Nspect)
-        return fail(LSX_EINVAL, "%s: wavelengths [%d, %d) are outside the grid's %d", who, (int)la0, (int)la0 + (int)nla, c->Nspect);
+    const int32_t nmu = s.nmu, ncol = s.ncol, nla = s.nla;
     const size_t plane = (size_t)nla * nmu, per = 4 * plane;
     if (!sink && nbytes != (size_t)ncol * per * 8) return fail(LSX_EINVAL, "%s: nbytes does not match [ncol][4][nla][nmu]", who);
+    if ((rc = stokes_check_state(c, who, s))) return rc;
     const int Ns = c->Nspace;
-    std::string msg;
-    if ((rc = lsxst::check_field((size_t)ncol * Ns, B, gammaB, chiB, msg))) return fail(rc, "%s: %s", who, msg.c_str());
-    if ((rc = lsxst::check_patterns(c->Nlines, ncomp, alpha, strength, shift, msg))) return fail(rc, "%s: %s", who, msg.c_str());
-    if ((rc = final_check_depths(c, who))) return rc;
-    if ((rc = final_check_columns(c, who, col0, ncol, FINAL_OTHER_ANGLE))) return rc;
-    // split profiles are formed from the kept broadening arrays, whether the context's own profiles depend on the ray or not
-    for (int q = col0; q < col0 + ncol && c->Nlines; ++q)
-        if (c->prof_kind.empty() || !c->prof_kind[q])
-            return fail(LSX_EUNSUPPORTED, "%s: the line profiles of column %d were handed over as arrays (lsx_set_columns): the library "
-                                          "cannot know them at another angle.  Build them with lsx_set_line_profiles or "
-                                          "lsx_set_atmosphere", who, q);
-    // the patterns of the lines that are active somewhere in the window
-    std::vector<uint8_t> wanted(std::max(1, c->Nlines), 0);
-    for (int t = 0; t < c->Ntrans; ++t) {
-        if (!c->htrans[t].is_line) continue;
-        const uint8_t* act = c->active.data() + (size_t)t * c->Nspect;
-        for (int la = la0; la < la0 + nla; ++la)
-            if (act[la]) { wanted[c->trans_row[t]] = 1; break; }
-    }
     std::vector<int32_t> pat_line;
     std::vector<double> pat_tab;
-    if ((rc = lsxst::pack_patterns(c->Nlines, ncomp, alpha, strength, shift, wanted, pat_line, pat_tab, msg)))
-        return fail(rc, "%s: %s", who, msg.c_str());
+    if ((rc = stokes_patterns(c, who, s, pat_line, pat_tab))) return rc;
     HIPCHK(hipSetDevice(c->device));
     if ((rc = final_tables(c, who))) return rc;
 
     // the tables of the call: [pat_line | pat_tab]
     const size_t line_bytes = (pat_line.size() * sizeof(int32_t) + 7) & ~(size_t)7;
-    const size_t tab_bytes = line_bytes + std::max<size_t>(1, pat_tab.size()) * 8;
-    if (c->stokes_tab_bytes < tab_bytes) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->d_stokes_tab) HIPCHK(hipFree(c->d_stokes_tab));
-        c->d_stokes_tab = nullptr;
-        c->stokes_tab_bytes = 0;
-        if ((rc = dmalloc(&c->d_stokes_tab, tab_bytes))) return rc;
-        c->stokes_tab_bytes = tab_bytes;
-    }
-    HIPCHK(hipMemcpyAsync(c->d_stokes_tab, pat_line.data(), pat_line.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    GrowBuf& tab = c->buf[BUF_STOKES_TAB];
+    if ((rc = tab.reserve(c, line_bytes + std::max<size_t>(1, pat_tab.size()) * 8))) return rc;
+    HIPCHK(hipMemcpyAsync(tab.p, pat_line.data(), pat_line.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     if (!pat_tab.empty())
-        HIPCHK(hipMemcpyAsync(c->d_stokes_tab + line_bytes, pat_tab.data(), pat_tab.size() * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(tab.p + line_bytes, pat_tab.data(), pat_tab.size() * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));                      // the host vectors may go out of scope on any return below
 
     // columns per pass: the field and the result of a pass stay under the cap (one column's need if that alone is more)
+    GrowBuf& work = c->buf[BUF_STOKES_WORK];
     const size_t head = ((size_t)nmu + 1) & ~(size_t)1;
     const size_t wcol = per + 3 * (size_t)Ns;
-    const size_t cap = c->stokes_work_cap ? c->stokes_work_cap : kWorkCapDefault;
-    const size_t chunk = std::max<size_t>(1, std::min<size_t>(std::min<size_t>(ncol, 65535), cap / (wcol * 8)));     // (and a grid's y limit)
-    const size_t need = head + chunk * wcol;
-    if (c->stokes_work_doubles < need) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->d_stokes_work) HIPCHK(hipFree(c->d_stokes_work));
-        c->d_stokes_work = nullptr;
-        c->stokes_work_doubles = 0;
-        if ((rc = dmalloc(&c->d_stokes_work, need))) return rc;
-        c->stokes_work_doubles = need;
-    }
-    double* d_mu = c->d_stokes_work;
+    const size_t chunk = pass_columns(ncol, work.cap, kWorkCapDefault, wcol, kGridYLimit);
+    if ((rc = work.reserve(c, (head + chunk * wcol) * 8))) return rc;
+    double* d_mu = work.as<double>();
     double* d_field = d_mu + head;
     double* d_out = d_field + chunk * 3 * (size_t)Ns;
-    HIPCHK(hipMemcpyAsync(d_mu, mu, (size_t)nmu * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_mu, s.mu, (size_t)nmu * 8, hipMemcpyHostToDevice, c->stream));
 
     StokesParams p{};
-    p.Ns = Ns; p.Nspect = c->Nspect; p.NLtot = c->NLtot; p.Natoms = c->Natoms; p.NlinesA = std::max(1, c->Nlines);
-    p.Ncont = c->Ncont; p.L = c->L; p.Nrays = c->Nrays; p.nmu = nmu; p.la0 = la0; p.nla = nla;
-    p.phi_compact = c->phi_compact; p.sca_per_lambda = c->sca_per_lambda; p.phi_G = c->phi_group;
+    final_fill(p, c);
+    final_fill_angles(p, c);
+    p.nmu = nmu; p.la0 = s.la0; p.nla = nla; p.mu = d_mu;
     p.ntab = (int32_t)pat_tab.size();
-    p.til_col = (int64_t)c->til_col; p.phi_col = (int64_t)c->phi_col; p.sca_col = (int64_t)c->sca_col;
-    p.wavelength = c->d_wavelength; p.u_la = c->d_u_la; p.exp2_tab = c->d_exp2_tab; p.voigt_W = c->d_voigt_w; p.mu = d_mu;
-    p.la_ptr = c->d_final_ptr; p.ents = c->d_final_ent; p.la_tile = c->d_final_tile;
-    p.height = c->d_height; p.temperature = c->d_temperature; p.n = c->d_n; p.nsr = c->d_nsr;
-    p.bnd = c->d_bnd;
-    p.bgchi_T = c->d_bgchi; p.bgeta_T = c->d_bgeta; p.J_T = c->d_J[c->jcur];      // what lsx_get(LSX_J) returns at this moment
-    p.E_T = c->d_E; p.sca = c->d_sca; p.phi_T = c->d_phi;
-    p.aDamp = c->d_aDamp; p.vBroad = c->d_vBroad; p.vlos = c->d_vlos; p.prof_kind = c->d_prof_kind;
-    p.pat_line = (const int32_t*)c->d_stokes_tab;
-    p.pat_tab = (const double*)(c->d_stokes_tab + line_bytes);
+    p.pat_line = tab.as<const int32_t>();
+    p.pat_tab = (const double*)(tab.p + line_bytes);
     p.field = d_field;
     p.out = d_out;
     const size_t lds = ((size_t)LSX_EXP_TAB + 64 + pat_tab.size() + lsxst::kCompDoubles) * 8;
 
     for (size_t b0 = 0; b0 < (size_t)ncol; b0 += chunk) {
         const size_t nb = std::min(chunk, (size_t)ncol - b0);
-        p.col0 = (int32_t)(col0 + b0);
+        p.col0 = (int32_t)(s.col0 + b0);
         p.fstride = (int64_t)(nb * Ns);
-        const double* const src[3] = {B, gammaB, chiB};
-        for (int a = 0; a < 3; ++a)
-            HIPCHK(hipMemcpyAsync(d_field + (size_t)a * nb * Ns, src[a] + b0 * Ns, nb * Ns * 8, hipMemcpyHostToDevice, c->stream));
+        if ((rc = stokes_upload_field(c, s, b0, nb, d_field))) return rc;
         const dim3 grid((unsigned)((nla + 63) / 64), (unsigned)nb);
         // angles in register chunks of NM.  The compiler's report decides the instances: NM = 1 is the only one
         // without a spilled vector register (NM = 2 spills 8, NM = 4 spills 20 into accumulator registers at one wave per SIMD), and
@@ -324,6 +317,6 @@ extern "C" int lsx_hip_stokes_rays(lsx_ctx* c, int32_t nmu, const double* mu, in
                                    const int32_t* ncomp, const int32_t* alpha, const double* strength, const double* shift,
                                    double* out, size_t nbytes)
 {
-    return stokes_rays_run(c, "lsx_hip_stokes_rays", nmu, mu, col0, ncol, la0, nla, B, gammaB, chiB, ncomp, alpha, strength, shift, out, nbytes,
-                           nullptr);
+    const StokesCall s{nmu, mu, col0, ncol, la0, nla, B, gammaB, chiB, ncomp, alpha, strength, shift};
+    return stokes_rays_run(c, "lsx_hip_stokes_rays", s, out, nbytes, nullptr);
 }

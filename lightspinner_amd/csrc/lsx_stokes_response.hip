@@ -208,69 +208,42 @@ __global__ void __launch_bounds__(64) k_response_walk(const RespParams p)
 
 extern "C" int lsx_hip_response_stokes_work_cap(lsx_ctx* c, size_t nbytes)
 {
-    if (!c) return fail(LSX_EINVAL, "lsx_hip_response_stokes_work_cap: null context");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (c->d_stresp_work) HIPCHK(hipFree(c->d_stresp_work));       // the next call allocates under the new cap
-    c->d_stresp_work = nullptr;
-    c->stresp_work_doubles = 0;
-    c->stresp_work_cap = nbytes;
-    return LSX_OK;
+    return GrowBuf::set_cap(c, BUF_STRESP_WORK, "lsx_hip_response_stokes_work_cap", nbytes);
 }
 
 // The argument rules of lsx_hip_response_stokes but the byte counts; nothing is launched.  (lsx_fit.hip asks them of its expanded
 // field before its first launch.)
-int lsxd::response_stokes_check(lsx_ctx* c, const char* who, int32_t nmu, const double* mu, int32_t col0, int32_t ncol, int32_t la0,
-                                int32_t nla, const double* B, const double* gammaB, const double* chiB, const int32_t* ncomp,
-                                const int32_t* alpha, const double* strength, const double* shift, uint32_t params,
-                                const double amplitude[3], int32_t nk, const int32_t* ks)
+int lsxd::response_stokes_check(lsx_ctx* c, const char* who, const StokesCall& s, uint32_t params, const double amplitude[3], int32_t nk,
+                                const int32_t* ks)
 {
     // ---- first what lsx_hip_stokes_rays checks, in its order ----
-    if (!c || !mu || !B || !gammaB || !chiB) return fail(LSX_EINVAL, "%s: null argument", who);
-    if (c->Nlines && !ncomp) return fail(LSX_EINVAL, "%s: null ncomp (one count per line; zeros for no pattern)", who);
-    int rc = final_check_angles(who, nmu, mu);
-    if (!rc) rc = final_check_range(c, who, col0, ncol);
+    int rc = stokes_check_call(c, who, s);
+    if (!rc) rc = stokes_check_state(c, who, s);
     if (rc) return rc;
-    if (nla < 1) return fail(LSX_EINVAL, "%s: nla = %d, need at least one wavelength", who, (int)nla);
-    if (la0 < 0 || (int64_t)la0 + nla > c->Nspect)
-        return fail(LSX_EINVAL, "%s: wavelengths [%d, %d) are outside the grid's %d", who, (int)la0, (int)la0 + (int)nla, c->Nspect);
+    // ---- ... then the response's own rules ----
     const int Ns = c->Nspace;
     std::string msg;
-    if ((rc = lsxst::check_field((size_t)ncol * Ns, B, gammaB, chiB, msg))) return fail(rc, "%s: %s", who, msg.c_str());
-    if ((rc = lsxst::check_patterns(c->Nlines, ncomp, alpha, strength, shift, msg))) return fail(rc, "%s: %s", who, msg.c_str());
-    if ((rc = final_check_depths(c, who))) return rc;
-    if ((rc = final_check_columns(c, who, col0, ncol, FINAL_OTHER_ANGLE))) return rc;
-    for (int q = col0; q < col0 + ncol && c->Nlines; ++q)
-        if (c->prof_kind.empty() || !c->prof_kind[q])
-            return fail(LSX_EUNSUPPORTED, "%s: the line profiles of column %d were handed over as arrays (lsx_set_columns): the library "
-                                          "cannot know them at another angle.  Build them with lsx_set_line_profiles or "
-                                          "lsx_set_atmosphere", who, q);
-    // ---- ... then the response's own rules ----
-    if ((rc = lsxst::check_response(params, amplitude, Ns, nk, ks, (size_t)ncol, col0, B, msg))) return fail(rc, "%s: %s", who, msg.c_str());
+    if ((rc = lsxst::check_response(params, amplitude, Ns, nk, ks, (size_t)s.ncol, s.col0, s.B, msg))) return fail(rc, "%s: %s", who, msg.c_str());
     int par[3] = {0, 0, 0};
     const int nvar = 1 + 2 * lsxst::response_params(params, par);
-    if ((int64_t)Ns * nvar > 65535 || nmu > 65535)
+    if ((int64_t)Ns * nvar > 65535 || s.nmu > 65535)
         return fail(LSX_EUNSUPPORTED, "%s: Nspace x (1 + 2 parameters) = %lld or nmu = %d is above a grid's 65535", who,
-                    (long long)Ns * nvar, (int)nmu);
+                    (long long)Ns * nvar, (int)s.nmu);
     return LSX_OK;
 }
 
 // The body of lsx_hip_response_stokes without its `stokes`.  sink null: the entry itself -- every pass is copied to rf.  An internal
 // caller (lsx_fit.hip) hands a sink instead and rf null: a pass's rf stays in the pass's device array and the sink is called in the
 // copy's place.  stokes_bytes: null, or the byte count of the entry's `stokes` to be checked with the others.
-int lsxd::response_stokes_run(lsx_ctx* c, const char* who, int32_t nmu, const double* mu, int32_t col0, int32_t ncol, int32_t la0,
-                              int32_t nla, const double* B, const double* gammaB, const double* chiB, const int32_t* ncomp,
-                              const int32_t* alpha, const double* strength, const double* shift, uint32_t params,
-                              const double amplitude[3], int32_t nk, const int32_t* ks, double* rf, size_t rf_bytes,
-                              const size_t* stokes_bytes, PassSink* sink)
+int lsxd::response_stokes_run(lsx_ctx* c, const char* who, const StokesCall& s, uint32_t params, const double amplitude[3], int32_t nk,
+                              const int32_t* ks, double* rf, size_t rf_bytes, const size_t* stokes_bytes, PassSink* sink)
 {
     // ---- everything is checked on the host before anything is launched ----
     if (!rf && !sink) return fail(LSX_EINVAL, "%s: null argument", who);
-    int rc = response_stokes_check(c, who, nmu, mu, col0, ncol, la0, nla, B, gammaB, chiB, ncomp, alpha, strength, shift, params, amplitude,
-                                   nk, ks);
+    int rc = response_stokes_check(c, who, s, params, amplitude, nk, ks);
     if (rc) return rc;
+    const int32_t nmu = s.nmu, ncol = s.ncol, nla = s.nla;
     const int Ns = c->Nspace;
-    std::string msg;
     int par[3] = {0, 0, 0};
     const int npar = lsxst::response_params(params, par);
     const int nvar = 1 + 2 * npar;
@@ -279,18 +252,9 @@ int lsxd::response_stokes_run(lsx_ctx* c, const char* who, int32_t nmu, const do
     if (!sink && rf_bytes != (size_t)ncol * per_rf * 8) return fail(LSX_EINVAL, "%s: rf_bytes does not match [ncol][npar][4][nla][nk][nmu]", who);
     if (stokes_bytes && *stokes_bytes != (size_t)ncol * 4 * plane * 8) return fail(LSX_EINVAL, "%s: stokes_bytes does not match [ncol][4][nla][nmu]", who);
 
-    // the patterns of the lines that are active somewhere in the window
-    std::vector<uint8_t> wanted(std::max(1, c->Nlines), 0);
-    for (int t = 0; t < c->Ntrans; ++t) {
-        if (!c->htrans[t].is_line) continue;
-        const uint8_t* act = c->active.data() + (size_t)t * c->Nspect;
-        for (int la = la0; la < la0 + nla; ++la)
-            if (act[la]) { wanted[c->trans_row[t]] = 1; break; }
-    }
     std::vector<int32_t> pat_line;
     std::vector<double> pat_tab;
-    if ((rc = lsxst::pack_patterns(c->Nlines, ncomp, alpha, strength, shift, wanted, pat_line, pat_tab, msg)))
-        return fail(rc, "%s: %s", who, msg.c_str());
+    if ((rc = stokes_patterns(c, who, s, pat_line, pat_tab))) return rc;
     HIPCHK(hipSetDevice(c->device));
     if ((rc = final_tables(c, who))) return rc;
 
@@ -307,63 +271,40 @@ int lsxd::response_stokes_run(lsx_ctx* c, const char* who, int32_t nmu, const do
     }
     const size_t int_bytes = (ints.size() * sizeof(int32_t) + 7) & ~(size_t)7;
     const double amps[4] = {amplitude[par[0]], amplitude[par[npar > 1 ? 1 : 0]], amplitude[par[npar > 2 ? 2 : 0]], 0.0};
-    const size_t tab_bytes = int_bytes + (4 + std::max<size_t>(1, pat_tab.size())) * 8;
-    if (c->stresp_tab_bytes < tab_bytes) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->d_stresp_tab) HIPCHK(hipFree(c->d_stresp_tab));
-        c->d_stresp_tab = nullptr;
-        c->stresp_tab_bytes = 0;
-        if ((rc = dmalloc(&c->d_stresp_tab, tab_bytes))) return rc;
-        c->stresp_tab_bytes = tab_bytes;
-    }
-    HIPCHK(hipMemcpyAsync(c->d_stresp_tab, ints.data(), ints.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->d_stresp_tab + int_bytes, amps, sizeof amps, hipMemcpyHostToDevice, c->stream));
+    GrowBuf& tab = c->buf[BUF_STRESP_TAB];
+    if ((rc = tab.reserve(c, int_bytes + (4 + std::max<size_t>(1, pat_tab.size())) * 8))) return rc;
+    HIPCHK(hipMemcpyAsync(tab.p, ints.data(), ints.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(tab.p + int_bytes, amps, sizeof amps, hipMemcpyHostToDevice, c->stream));
     if (!pat_tab.empty())
-        HIPCHK(hipMemcpyAsync(c->d_stresp_tab + int_bytes + sizeof amps, pat_tab.data(), pat_tab.size() * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(tab.p + int_bytes + sizeof amps, pat_tab.data(), pat_tab.size() * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));                      // the host vectors may go out of scope on any return below
 
     // columns per pass: the arrays of a pass stay under the cap (one column's need if that alone is more)
+    GrowBuf& work = c->buf[BUF_STRESP_WORK];
     const size_t nblk = ((size_t)nla + 63) / 64, nlaP = nblk * 64;
     const size_t head = ((size_t)nmu + 1) & ~(size_t)1;
     const size_t w_nodes = (size_t)nmu * nvar * Ns * lsxst::kNodeDoubles * nlaP, w_state = (size_t)nmu * Ns * lsxst::kStateDoubles * nlaP;
     const size_t wcol = w_nodes + w_state + per_rf + 3 * (size_t)Ns;
-    const size_t cap = c->stresp_work_cap ? c->stresp_work_cap : kWorkCapDefault;
-    const size_t chunk = std::max<size_t>(1, std::min<size_t>(std::min<size_t>(ncol, 65535), cap / (wcol * 8)));     // (and a grid's y limit)
-    const size_t need = head + chunk * wcol;
-    if (c->stresp_work_doubles < need) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->d_stresp_work) HIPCHK(hipFree(c->d_stresp_work));
-        c->d_stresp_work = nullptr;
-        c->stresp_work_doubles = 0;
-        if ((rc = dmalloc(&c->d_stresp_work, need))) return rc;
-        c->stresp_work_doubles = need;
-    }
-    double* d_mu = c->d_stresp_work;
+    const size_t chunk = pass_columns(ncol, work.cap, kWorkCapDefault, wcol, kGridYLimit);
+    if ((rc = work.reserve(c, (head + chunk * wcol) * 8))) return rc;
+    double* d_mu = work.as<double>();
     double* d_field = d_mu + head;
     double* d_nodes = d_field + chunk * 3 * (size_t)Ns;
     double* d_state = d_nodes + chunk * w_nodes;
     double* d_rf = d_state + chunk * w_state;
-    HIPCHK(hipMemcpyAsync(d_mu, mu, (size_t)nmu * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d_mu, s.mu, (size_t)nmu * 8, hipMemcpyHostToDevice, c->stream));
 
     RespParams p{};
-    p.Ns = Ns; p.Nspect = c->Nspect; p.NLtot = c->NLtot; p.Natoms = c->Natoms; p.NlinesA = std::max(1, c->Nlines);
-    p.Ncont = c->Ncont; p.L = c->L; p.Nrays = c->Nrays; p.nmu = nmu; p.la0 = la0; p.nla = nla;
-    p.phi_compact = c->phi_compact; p.sca_per_lambda = c->sca_per_lambda; p.phi_G = c->phi_group;
+    final_fill(p, c);
+    final_fill_angles(p, c);
+    p.nmu = nmu; p.la0 = s.la0; p.nla = nla; p.mu = d_mu;
     p.ntab = (int32_t)pat_tab.size();
-    p.til_col = (int64_t)c->til_col; p.phi_col = (int64_t)c->phi_col; p.sca_col = (int64_t)c->sca_col;
-    p.wavelength = c->d_wavelength; p.u_la = c->d_u_la; p.exp2_tab = c->d_exp2_tab; p.voigt_W = c->d_voigt_w; p.mu = d_mu;
-    p.la_ptr = c->d_final_ptr; p.ents = c->d_final_ent; p.la_tile = c->d_final_tile;
-    p.height = c->d_height; p.temperature = c->d_temperature; p.n = c->d_n; p.nsr = c->d_nsr;
-    p.bnd = c->d_bnd;
-    p.bgchi_T = c->d_bgchi; p.bgeta_T = c->d_bgeta; p.J_T = c->d_J[c->jcur];      // what lsx_get(LSX_J) returns at this moment
-    p.E_T = c->d_E; p.sca = c->d_sca; p.phi_T = c->d_phi;
-    p.aDamp = c->d_aDamp; p.vBroad = c->d_vBroad; p.vlos = c->d_vlos; p.prof_kind = c->d_prof_kind;
-    const int32_t* d_ints = (const int32_t*)c->d_stresp_tab;
+    const int32_t* d_ints = tab.as<const int32_t>();
     p.pat_line = d_ints;
     p.kreq = d_ints + o_kreq;
     p.ks = ks ? d_ints + o_ks : nullptr;
     p.par = d_ints + o_par;
-    p.amp = (const double*)(c->d_stresp_tab + int_bytes);
+    p.amp = (const double*)(tab.p + int_bytes);
     p.pat_tab = p.amp + 4;
     p.field = d_field;
     p.npar = npar; p.nvar = nvar; p.nk = nkk; p.nlaP = (int32_t)nlaP;
@@ -373,11 +314,9 @@ int lsxd::response_stokes_run(lsx_ctx* c, const char* who, int32_t nmu, const do
 
     for (size_t b0 = 0; b0 < (size_t)ncol; b0 += chunk) {
         const size_t nb = std::min(chunk, (size_t)ncol - b0);
-        p.col0 = (int32_t)(col0 + b0);
+        p.col0 = (int32_t)(s.col0 + b0);
         p.fstride = (int64_t)(nb * Ns);
-        const double* const src[3] = {B, gammaB, chiB};
-        for (int a = 0; a < 3; ++a)
-            HIPCHK(hipMemcpyAsync(d_field + (size_t)a * nb * Ns, src[a] + b0 * Ns, nb * Ns * 8, hipMemcpyHostToDevice, c->stream));
+        if ((rc = stokes_upload_field(c, s, b0, nb, d_field))) return rc;
         // one launch of the nodes per angle (the profile function is evaluated per angle, as in lsx_stokes.hip), one of the walks for all
         for (int m0 = 0; m0 < nmu; ++m0) {
             p.mu0 = m0;
@@ -404,13 +343,13 @@ extern "C" int lsx_hip_response_stokes(lsx_ctx* c, int32_t nmu, const double* mu
 {
     const char* who = "lsx_hip_response_stokes";
     if (!rf) return fail(LSX_EINVAL, "%s: null argument", who);
-    const int rc = response_stokes_run(c, who, nmu, mu, col0, ncol, la0, nla, B, gammaB, chiB, ncomp, alpha, strength, shift, params, amplitude,
-                                       nk, ks, rf, rf_bytes, stokes ? &stokes_bytes : nullptr, nullptr);
+    const StokesCall s{nmu, mu, col0, ncol, la0, nla, B, gammaB, chiB, ncomp, alpha, strength, shift};
+    const int rc = response_stokes_run(c, who, s, params, amplitude, nk, ks, rf, rf_bytes, stokes ? &stokes_bytes : nullptr, nullptr);
     if (rc) return rc;
     // The vector of the call's own field comes from the Stokes pass itself, so that it has that pass's bits by construction.  The
     // walk up forms the same vector through the same functions (the host build's is bit for bit lsx_stokes_host_window's), but in
     // another kernel the device compiler contracts products and sums into fused operations differently: measured on an MI355X, a
     // quarter of the entries differ from k_stokes_rays' in the last bits (at most 1.2e-14 of I).  One more launch per angle
-    if (stokes) return lsx_hip_stokes_rays(c, nmu, mu, col0, ncol, la0, nla, B, gammaB, chiB, ncomp, alpha, strength, shift, stokes, stokes_bytes);
+    if (stokes) return stokes_rays_run(c, "lsx_hip_stokes_rays", s, stokes, stokes_bytes, nullptr);
     return LSX_OK;
 }

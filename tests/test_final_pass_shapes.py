@@ -11,7 +11,10 @@ ratio to the bound.  Every call here is an ordinary valid call.
 
 Measured on the MI355X, worst over all cases and both rules ("The final pass off the FALC shape"): rates 4.5e-15
 relative, < 0.001 x the bound; emergent rays 4.0e-13, 0.032 x; quadrature angles against LSX_I 5.5e-13, 0.041 x; depth rays I(k)
-4.1e-13, 0.032 x; spectrum 9.7e-14, 0.009 x."""
+4.1e-13, 0.032 x; spectrum 9.7e-14, 0.009 x.
+
+Last, the seven entries whose passes run under a cap (these four without the emergent rays, the Stokes pass, its response and the
+field fit) one after the other on one context, bit for bit against fresh contexts."""
 import numpy as np
 import pytest
 
@@ -178,4 +181,80 @@ def test_spectrum_meets_the_oracle(hip_lib, oracle_lib, name, solver):
     tsp.inside(tag + ', interpolation mode', interp, sc.envelope_spectrum(oracle_lib, prob, blk, prof, mus, n, J, w, alpha, None, solver))
     assert not np.array_equal(given, interp)
     assert np.array_equal(e.emergent_spectrum(mus, w, alpha=alpha, col0=1, ncol=2), interp[1:3])
+    e.close()
+
+
+# ---- the seven capped passes on one context ------------------------------------------------------------------------------------------
+def test_the_capped_passes_keep_their_own_buffers_on_one_context(hip_lib):
+    """Rates, losses, depth rays, spectrum, Stokes rays, their response and the field fit keep their passes under a cap each, in a
+    buffer each (lsx_ctx.h, GrowBuf).  On ONE context, one after the other: first every cap at one column's need -- three passes an
+    entry, every work buffer freed and allocated anew -- then every cap back at its default.  Every result is, bit for bit, that of
+    the same call on a fresh context that has seen no other call: no two passes on the same storage (the fit holds its buffer while
+    the Stokes pass and the response run inside it, the response entry runs the Stokes pass behind its own), every cap at its own
+    buffer."""
+    import fit_cases as fc
+    import stokes_cases as stc
+    import stokes_response_cases as src
+    from lightspinner_amd.problem import Engine, RadiativeLosses
+    from lightspinner_amd import synth
+    Ns, ncol, nnode = 3, 3, (2, 2, 2)
+    prob, block, prof, J = stc.problem(Ns, ncol, vlos=True)
+    fld, pats, mus = stc.field(Ns, ncol), stc.PATTERN_SETS['all'], fc.MUS
+    nmu, nla, P = mus.shape[0], prob.Nspect, sum(nnode)
+    w = fp.made_up_wanted(prob)
+    alpha, bg = sc.interp_alpha(prob, w), fp.given_background(prob, block, w)
+    bgkw = dict(bg_chi=bg[0], bg_eta=bg[1], **({'bg_sca': bg[2]} if prob.sca_per_lambda else {}))
+    basis, nodes = fc.basis_of(Ns, nnode), fc.nodes_of(fld, Ns, nnode)
+
+    def fresh():
+        e = Engine(prob, ncol, lib=hip_lib)
+        synth.load_columns(e, block, prof)
+        e.set(LSX_J, J)
+        return e
+
+    def stokes(e, **kw):
+        r = e.stokes_rays(mus, *fld, patterns=pats, **kw)
+        return [r.I, r.Q, r.U, r.V]
+
+    e0 = fresh()
+    obs = np.stack(stokes(e0), axis=1) * 1.01
+    e0.close()
+
+    def response(e, **kw):
+        r = e.stokes_response(mus, *fld, patterns=pats, amplitudes=src.AMPS, **kw)
+        return [src.stack_rf(r), r.stokes.I, r.stokes.Q, r.stokes.U, r.stokes.V]
+
+    def fit(e, **kw):
+        ne = e.fit_field_normal(mus, basis, nnode, nodes, obs, patterns=pats, amplitudes=fc.AMPS, **kw)
+        step = e.fit_field_step(ne.hess, ne.grad, 1.0, nodes)               # (the step lays its own arrays out in the fit's buffer)
+        c2 = e.fit_field_chi2(mus, basis, nnode, nodes, obs, patterns=pats)[0]
+        return [ne.chi2, ne.grad, ne.hess, ne.field, c2, *step]
+
+    # one column's need of every pass in bytes, as the units count it (their "columns per pass" paragraphs)
+    nlaP, nw, M = 64 * ((nla + 63) // 64), w.shape[0], 4 * nla * nmu
+    nstream = 3 if prob.sca_per_lambda else 2
+    passes = [
+        ('rates', lambda e, **kw: [getattr(e.radiative_rates(**kw), f) for f in ('Rij', 'Rji', 'Rji_ref')], Ns * (prob.Nspect + 2 * prob.SNl)),
+        ('losses', lambda e, **kw: [getattr(e.radiative_losses(what=RadiativeLosses.FIELDS, **kw), f) for f in RadiativeLosses.FIELDS],
+         Ns * (3 * prob.Nspect + 2 * prob.SNl)),
+        ('depth', lambda e, **kw: [getattr(e.depth_rays(mus, **kw), f) for f in tdr.FIELDS], 5 * nmu * nla * Ns + nmu * nla),
+        ('spectrum', lambda e, **kw: [e.emergent_spectrum(mus, w, alpha=alpha, **bgkw, **kw)], nw * nmu + 2 * nstream * nw * Ns),
+        ('stokes', stokes, M + 3 * Ns),
+        ('response', response, nmu * 7 * Ns * 11 * nlaP + nmu * Ns * 5 * nlaP + 3 * M * Ns + 3 * Ns),
+        ('fit', fit, 2 * M + 2 * M + P * M + 1 + P + P * P),
+    ]
+    want = {}
+    for name, run, _ in passes:
+        e0 = fresh()
+        want[name] = run(e0)
+        finite = want[name][:-1] if name == 'depth' else want[name]           # (a height of tau = 1 need not exist)
+        assert all(np.all(np.isfinite(a)) for a in finite), name
+        e0.close()
+    e = fresh()
+    for rnd, cap_of in (('one column a pass', lambda doubles: 8 * doubles), ('default caps', lambda doubles: 0)):
+        for name, run, doubles in passes:
+            got = run(e, work_cap_bytes=cap_of(doubles))
+            assert len(got) == len(want[name])
+            for i, (a, b) in enumerate(zip(got, want[name])):
+                assert np.array_equal(a, b, equal_nan=True), (rnd, name, i)
     e.close()

@@ -195,3 +195,58 @@ def test_import_asks_for_eight_hardware_queues_unless_the_caller_has_chosen():
         out = subprocess.run([sys.executable, '-c', code], cwd=root, env=env, capture_output=True, text=True, timeout=300)
         assert out.returncode == 0, out.stderr
         assert out.stdout.strip() == expect
+
+
+# ---- the columns of a final pass (lsx_plan.h, pass_columns) ----------------------------------------------------------------------------
+DEFAULT_CAP = 256 << 20             # the default of most of the units' headers
+Y_LIMIT = 65535                     # a launch grid's y
+
+
+@pytest.fixture(scope='module')
+def pass_columns():
+    """the rule as the entries call it, from the product's host-only sources (`make host`, lsx_plan_capi.cpp)"""
+    import ctypes as C
+    import subprocess
+    csrc = os.path.join(ROOT, 'lightspinner_amd', 'csrc')
+    subprocess.check_call(['make', '-s', '-C', csrc, 'host'])
+    f = C.CDLL(os.path.join(csrc, 'liblsx_host.so')).lsx_plan_pass_columns
+    f.restype = C.c_uint64
+    f.argtypes = [C.c_uint64] * 5
+    return lambda ncol, cap, wcol, default=DEFAULT_CAP, limit=Y_LIMIT: int(f(ncol, cap, default, wcol, limit))
+
+
+def expected_columns(ncol, cap, wcol, default=DEFAULT_CAP, limit=Y_LIMIT):
+    """max(1, min(min(ncol, limit), cap / (8 wcol))), cap 0 the default: in Python's integers"""
+    return max(1, min(min(ncol, limit), (cap if cap else default) // (8 * wcol)))
+
+
+@pytest.mark.parametrize('what,ncol,cap,wcol', [
+    ('cap 0 takes the default', 10 ** 6, 0, 1000),
+    ('cap 0 takes the default: a small one', 10 ** 6, 0, 10 ** 6),
+    ('one column alone above the cap', 7, 8 * 1000 - 1, 1000),
+    ('one column alone far above the cap', 7, 1, 10 ** 9),
+    ('ncol below the quotient', 5, 8 * 1000 * 6, 1000),
+    ('ncol at the quotient', 6, 8 * 1000 * 6, 1000),
+    ('a quotient above the grid limit with ncol above it', 70000, 8 * 3 * 65536, 3),
+    ('a quotient above the grid limit with ncol at it', 65535, 8 * 3 * 65536, 3),
+    ('a quotient one below the grid limit', 70000, 8 * 3 * 65534, 3),
+    ('a cap that is exactly a multiple', 100, 8 * 1234 * 17, 1234),
+    ('a cap one byte less', 100, 8 * 1234 * 17 - 1, 1234),
+    ('a cap one byte more', 100, 8 * 1234 * 17 + 1, 1234),
+])
+def test_pass_columns_at_its_edges(pass_columns, what, ncol, cap, wcol):
+    assert pass_columns(ncol, cap, wcol) == expected_columns(ncol, cap, wcol), what
+
+
+def test_pass_columns_values_and_the_entry_without_a_limit(pass_columns):
+    """the edges by their numbers, so that the expectation above cannot be wrong the same way; lsx_hip_radiative_rates and
+    lsx_hip_fit_field_step pass no limit"""
+    assert pass_columns(10 ** 6, 0, 1000) == (256 << 20) // 8000 == 33554
+    assert pass_columns(10 ** 6, 0, 1000, default=64 << 20) == (64 << 20) // 8000           # the fit's default
+    assert pass_columns(7, 7999, 1000) == 1 and pass_columns(7, 1, 10 ** 9) == 1
+    assert pass_columns(5, 48000, 1000) == 5
+    assert pass_columns(70000, 8 * 3 * 65536, 3) == 65535
+    assert pass_columns(100, 8 * 1234 * 17, 1234) == 17 and pass_columns(100, 8 * 1234 * 17 - 1, 1234) == 16
+    no_limit = 2 ** 64 - 1
+    assert pass_columns(70000, 8 * 3 * 65536, 3, limit=no_limit) == 65536
+    assert pass_columns(70000, 0, 3, limit=no_limit) == 70000
