@@ -68,11 +68,26 @@ int lsx_hip_fit_field_step(lsx_ctx* ctx, int32_t ncol, int32_t P, const double* 
 
 /* The cap of the fit's own device memory in bytes for this context (0: the default, 64 MiB): per column 3 x 4 nla nmu doubles for
  * obs, weight and S, (P + 2) x 4 nla nmu for the Jacobian, the residual and the weight in use, and the sums; the columns of a call
- * are taken in groups that stay under it (one column's need where that alone is more).  The passes it runs keep their own caps.
+ * are taken in groups that stay under it (one column's need where that alone is more).  With an instrument (below) obs, weight, the
+ * residual, the weight in use, S' and J' are over M' = 4 nobs nmu points a column, S and J over M = 4 nla nmu as before:
+ * (4 + P) M' + (1 + P) M doubles and the sums.  The passes it runs keep their own caps.
  * Frees what is allocated.  The results do not depend on it. */
 int lsx_hip_fit_field_work_cap(lsx_ctx* ctx, size_t nbytes);
+
+/* The instrument: a banded matrix over the wavelengths of a call's window, shared by all columns, Stokes parameters and angles of
+ * the call as `basis` is.  An observed point is
+ *     S'[s][o][m] = sum_{i = 0 .. width - 1} weight[o][i] S[s][first[o] + i][m]        i ascending, from 0.0
+ * and so is every row of the Jacobian.  The entries that take one are declared in lsx_hip_fit_instrument.h. */
+typedef struct lsx_fit_instrument {
+    int32_t nobs, width;      /* pixels; grid points a pixel reads: 1 <= width <= nla                */
+    const int32_t* first;     /* [nobs]: 0 <= first[o] <= nla - width                               */
+    const double*  weight;    /* [nobs][width], finite, any sign; pad a shorter row with zeros       */
+} lsx_fit_instrument;
 
 #ifdef __cplusplus
 }
 #endif
+
+#include "lsx_hip_fit_instrument.h"
+
 #endif /* LSX_HIP_FIT_H */

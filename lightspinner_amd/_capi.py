@@ -24,6 +24,10 @@ ERRORS = {1: 'LSX_EINVAL', 2: 'LSX_EDEVICE', 3: 'LSX_ESINGULAR', 5: 'LSX_EUNSUPP
 _dp = C.POINTER(C.c_double)
 
 
+class LsxFitInstrument(C.Structure):            # include/lsx_hip_fit.h
+    _fields_ = [('nobs', C.c_int32), ('width', C.c_int32), ('first', C.POINTER(C.c_int32)), ('weight', _dp)]
+
+
 class LsxTransition(C.Structure):
     _fields_ = [('atom', C.c_int32), ('is_line', C.c_int32), ('i', C.c_int32), ('j', C.c_int32),
                 ('Nblue', C.c_int32), ('Nlambda', C.c_int32),
@@ -270,6 +274,17 @@ class LsxLibrary:
             d.lsx_hip_fit_field_step.restype = C.c_int
             d.lsx_hip_fit_field_work_cap.argtypes = [C.c_void_p, C.c_size_t]
             d.lsx_hip_fit_field_work_cap.restype = C.c_int
+        self.has_fit_instrument = hasattr(d, 'lsx_hip_instrument_fit_normal')      # include/lsx_hip_fit_instrument.h
+        if self.has_fit_instrument:
+            ip32 = C.POINTER(C.c_int32)
+            inst = C.POINTER(LsxFitInstrument)
+            head = [C.c_void_p, C.c_int32, _dp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, ip32, ip32, _dp, _dp, ip32, _dp, _dp, _dp]
+            d.lsx_hip_instrument_fit_normal.argtypes = head + [_dp, _dp, _dp, _dp, _dp, _dp, _dp, inst]
+            d.lsx_hip_instrument_fit_normal.restype = C.c_int
+            d.lsx_hip_instrument_fit_chi2.argtypes = head + [_dp, _dp, _dp, _dp, inst]
+            d.lsx_hip_instrument_fit_chi2.restype = C.c_int
+            d.lsx_hip_instrument_apply.argtypes = [C.c_void_p, inst, C.c_int32, C.c_int32, C.c_int32, _dp, _dp]
+            d.lsx_hip_instrument_apply.restype = C.c_int
         self.has_background = hasattr(d, 'lsx_hip_background')         # include/lsx_hip_background.h
         if self.has_background:
             ip32 = C.POINTER(C.c_int32)

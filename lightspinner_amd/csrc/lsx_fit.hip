@@ -14,6 +14,9 @@
 //                   writer per value, no atomics; the order depends on M alone.
 // lsx_hip_fit_field_chi2 runs the Stokes pass, the last z of k_fit_jac and the last entry of k_fit_reduce: the same instructions on the
 // same numbers, hence the same bits.
+// With an instrument (include/lsx_hip_fit_instrument.h) k_fit_jac forms the rows of J on the grid as above, k_fit_smear
+// (lsx_fit_instrument.hip) forms J' and S' from them and from S, the z = P slice of k_fit_jac forms the weight and the residual over
+// the M' = 4 nobs nmu observed points, and k_fit_reduce runs with M' in the place of M.  Without one nothing here changes.
 //   k_fit_step    lane = column: lsxfit::step_solve / step_finish with the packed triangle and the right-hand side in LDS, element e of
 //                 lane l at [e][l] as solve_mem has its work space (lsx_solve_dev.h).
 #include <hip/hip_runtime.h>
@@ -27,6 +30,7 @@
 #include "lsx_ctx.h"
 #include "lsx_final_host.h"
 #include "lsx_fit_dev.h"
+#include "lsx_fit_inst.h"
 #include "lsx_stokes_prep.h"
 
 using namespace lsxd;
@@ -145,6 +149,28 @@ struct KeepStokes final : PassSink {
     }
 };
 
+// the same with an instrument: p is the reduction's (M = M', J = J', S = S'), grid the Jacobian's on the window's wavelengths
+void launch_sums_inst(lsx_ctx* c, const FitParams& p, FitSmear f, const FitParams& grid, size_t b0, size_t nb, const double* d_rf, bool normal)
+{
+    const int nent = lsxfit::entries(p.P);
+    if (normal) {
+        FitParams g = grid;
+        g.cl0 = (int32_t)b0;
+        g.rf = d_rf;
+        hipLaunchKernelGGL(k_fit_jac, dim3((unsigned)((g.M + 63) / 64), (unsigned)nb, (unsigned)g.P), dim3(64), (size_t)g.Ns * 8, c->stream, g);
+    } else {
+        f.P = 0;                      // the Stokes vector alone
+    }
+    fit_smear_launch(c, f, b0, nb);
+    FitParams q = p;                  // the residual's slice of k_fit_jac over the observed points
+    q.cl0 = (int32_t)b0;
+    q.P = 0;
+    hipLaunchKernelGGL(k_fit_jac, dim3((unsigned)((q.M + 63) / 64), (unsigned)nb, 1u), dim3(64), (size_t)q.Ns * 8, c->stream, q);
+    q.P = p.P;
+    q.e0 = normal ? 0 : nent - 1;
+    hipLaunchKernelGGL(k_fit_reduce, dim3(normal ? (unsigned)nent : 1u, (unsigned)nb), dim3(lsxfit::kReduceLanes), 0, c->stream, q);
+}
+
 void launch_sums(lsx_ctx* c, FitParams p, size_t b0, size_t nb, const double* d_rf, bool normal)
 {
     p.cl0 = (int32_t)b0;
@@ -168,10 +194,13 @@ void launch_sums(lsx_ctx* c, FitParams p, size_t b0, size_t nb, const double* d_
 // the sink of the response pass: the sums of the pass's columns from the pass's rf
 struct SumPass final : PassSink {
     lsx_ctx* c;
-    FitParams p;
+    FitParams p, grid;
+    FitSmear smear;
+    bool inst;
     int pass(size_t b0, size_t nb, const double* d_rf) override
     {
-        launch_sums(c, p, b0, nb, d_rf, true);
+        if (inst) launch_sums_inst(c, p, smear, grid, b0, nb, d_rf, true);
+        else launch_sums(c, p, b0, nb, d_rf, true);
         HIPCHK(hipGetLastError());
         return LSX_OK;
     }
@@ -181,7 +210,7 @@ struct SumPass final : PassSink {
 int fit_run(lsx_ctx* c, const char* who, bool normal, int32_t nmu, const double* mu, int32_t col0, int32_t ncol, int32_t la0, int32_t nla,
             const int32_t* ncomp, const int32_t* alpha, const double* strength, const double* shift, const int32_t* nnode,
             const double* basis, const double* base, const double* nodes, const double* amplitude, const double* obs,
-            const double* weight, double* chi2, double* grad, double* hess, double* field_out)
+            const double* weight, double* chi2, double* grad, double* hess, double* field_out, const lsx_fit_instrument* inst)
 {
     // ---- everything is checked on the host before anything is launched ----
     if (!c || !mu || !nnode || !basis || !nodes || !obs || !chi2 || (normal && (!grad || !hess || !amplitude)))
@@ -190,6 +219,7 @@ int fit_run(lsx_ctx* c, const char* who, bool normal, int32_t nmu, const double*
     if (!rc) rc = final_check_range(c, who, col0, ncol);
     if (!rc) rc = final_check_window(c, who, la0, nla);
     if (rc) return rc;
+    if (inst && (rc = fit_instrument_check(who, inst, nla, nmu, 4))) return rc;
     int64_t Psum = 0;
     for (int a = 0; a < 3; ++a) {
         if (nnode[a] < 0) return fail(LSX_EINVAL, "%s: nnode[%d] = %d is negative", who, a, (int)nnode[a]);
@@ -199,7 +229,8 @@ int fit_run(lsx_ctx* c, const char* who, bool normal, int32_t nmu, const double*
         return fail(LSX_EINVAL, "%s: %lld node values; between 1 and %d can be fitted", who, (long long)Psum, LSX_FIT_MAX_PARAMS);
     const int P = (int)Psum, Ns = c->Nspace;
     if ((int64_t)4 * nla * nmu > INT32_MAX / 2) return fail(LSX_EUNSUPPORTED, "%s: 4 nla nmu = %lld data points a column", who, 4LL * nla * nmu);
-    const size_t M = (size_t)4 * nla * nmu, NC = (size_t)ncol;
+    const size_t Mg = (size_t)4 * nla * nmu, NC = (size_t)ncol;       // the points of the window's grid a column
+    const size_t M = inst ? (size_t)4 * inst->nobs * nmu : Mg;        // the data points a column
     size_t bad = 0;
     if (!all_finite(basis, (size_t)P * Ns, bad))
         return fail(LSX_EINVAL, "%s: basis[%zu][%zu] is not finite", who, bad / Ns, bad % Ns);
@@ -242,12 +273,14 @@ int fit_run(lsx_ctx* c, const char* who, bool normal, int32_t nmu, const double*
     HIPCHK(hipSetDevice(c->device));
     const size_t nW = weight ? 1 : 0;
     const size_t sums = 1 + (normal ? (size_t)P + (size_t)P * P : 0);
-    const size_t wcol = (2 + nW) * M + 2 * M + (normal ? (size_t)P * M : 0) + sums;      // obs, S, weight; R, W; J; the sums
-    const size_t head = (size_t)P * Ns;
+    // obs, S, weight; R, W; J; the sums -- with an instrument S and J on the grid besides S' and J' on the pixels
+    const size_t wcol = (2 + nW) * M + 2 * M + (normal ? (size_t)P * M : 0) + sums + (inst ? Mg + (normal ? (size_t)P * Mg : 0) : 0);
+    const size_t head = (size_t)P * Ns + (inst ? fit_instrument_doubles(inst) : 0);
     GrowBuf& work = c->buf[BUF_FIT_WORK];
     const size_t G = pass_columns(NC, work.cap, kWorkCapDefault, wcol, kGridYLimit);
     if ((rc = work.reserve(c, (head + G * wcol) * 8))) return rc;
     double* d_basis = work.as<double>();
+    double* d_inst = d_basis + (size_t)P * Ns;
     double* d_obs = d_basis + head;
     double* d_S = d_obs + G * M;
     double* d_wt = d_S + G * M;
@@ -257,7 +290,10 @@ int fit_run(lsx_ctx* c, const char* who, bool normal, int32_t nmu, const double*
     double* d_chi2 = d_J + (normal ? G * P * M : 0);
     double* d_grad = d_chi2 + G;
     double* d_hess = d_grad + (normal ? G * P : 0);
-    HIPCHK(hipMemcpyAsync(d_basis, basis, head * 8, hipMemcpyHostToDevice, c->stream));
+    double* d_Sg = d_hess + (normal ? G * P * P : 0);                 // with an instrument: S and J on the grid
+    double* d_Jg = d_Sg + G * Mg;
+    HIPCHK(hipMemcpyAsync(d_basis, basis, (size_t)P * Ns * 8, hipMemcpyHostToDevice, c->stream));
+    if (inst && (rc = fit_instrument_upload(c, inst, d_inst))) return rc;
 
     FitParams p{};
     p.Ns = Ns; p.nla = nla; p.nmu = nmu; p.M = (int32_t)M; p.P = P;
@@ -267,6 +303,12 @@ int fit_run(lsx_ctx* c, const char* who, bool normal, int32_t nmu, const double*
         for (int n = 0; n < nnode[par[i]]; ++n) p.row_par[j++] = (int8_t)i;
     p.basis = d_basis; p.obs = d_obs; p.weight = weight ? d_wt : nullptr; p.S = d_S;
     p.R = d_R; p.W = d_W; p.J = d_J; p.chi2 = d_chi2; p.grad = d_grad; p.hess = d_hess;
+    FitParams grid = p;               // with an instrument: k_fit_jac's rows on the grid; p is what is reduced
+    FitSmear smear{};
+    if (inst) {
+        grid.M = (int32_t)Mg; grid.J = d_Jg; grid.S = d_Sg;
+        smear = FitSmear{4, nla, nmu, inst->nobs, inst->width, P, d_inst, d_Jg, d_Sg, d_J, d_S};
+    }
 
     for (size_t g0 = 0; g0 < NC; g0 += G) {
         const size_t ng = std::min(G, NC - g0);
@@ -274,14 +316,15 @@ int fit_run(lsx_ctx* c, const char* who, bool normal, int32_t nmu, const double*
         if (weight) HIPCHK(hipMemcpyAsync(d_wt, weight + g0 * M, ng * M * 8, hipMemcpyHostToDevice, c->stream));
         const StokesCall s = call(g0, ng);
         KeepStokes keep;
-        keep.c = c; keep.d_S = d_S; keep.M = M;
+        keep.c = c; keep.d_S = inst ? d_Sg : d_S; keep.M = Mg;
         if ((rc = stokes_rays_run(c, who, s, nullptr, 0, &keep))) return rc;
         if (normal) {
             SumPass sum;
-            sum.c = c; sum.p = p;
+            sum.c = c; sum.p = p; sum.grid = grid; sum.smear = smear; sum.inst = inst != nullptr;
             if ((rc = response_stokes_run(c, who, s, params, amplitude, 0, nullptr, nullptr, 0, nullptr, &sum))) return rc;
         } else {
-            launch_sums(c, p, 0, ng, nullptr, false);
+            if (inst) launch_sums_inst(c, p, smear, grid, 0, ng, nullptr, false);
+            else launch_sums(c, p, 0, ng, nullptr, false);
             HIPCHK(hipGetLastError());
         }
         HIPCHK(hipMemcpyAsync(chi2 + g0, d_chi2, ng * 8, hipMemcpyDeviceToHost, c->stream));
@@ -308,7 +351,7 @@ extern "C" int lsx_hip_fit_field_normal(lsx_ctx* c, int32_t nmu, const double* m
                                         double* chi2, double* grad, double* hess, double* field_out)
 {
     return fit_run(c, "lsx_hip_fit_field_normal", true, nmu, mu, col0, ncol, la0, nla, ncomp, alpha, strength, shift, nnode, basis, base,
-                   nodes, amplitude, obs, weight, chi2, grad, hess, field_out);
+                   nodes, amplitude, obs, weight, chi2, grad, hess, field_out, nullptr);
 }
 
 extern "C" int lsx_hip_fit_field_chi2(lsx_ctx* c, int32_t nmu, const double* mu, int32_t col0, int32_t ncol, int32_t la0, int32_t nla,
@@ -317,7 +360,34 @@ extern "C" int lsx_hip_fit_field_chi2(lsx_ctx* c, int32_t nmu, const double* mu,
                                       const double* obs, const double* weight, double* chi2, double* field_out)
 {
     return fit_run(c, "lsx_hip_fit_field_chi2", false, nmu, mu, col0, ncol, la0, nla, ncomp, alpha, strength, shift, nnode, basis, base, nodes,
-                   nullptr, obs, weight, chi2, nullptr, nullptr, field_out);
+                   nullptr, obs, weight, chi2, nullptr, nullptr, field_out, nullptr);
+}
+
+// through an instrument (include/lsx_hip_fit_instrument.h); inst == NULL: the two entries above
+extern "C" int lsx_hip_instrument_fit_normal(lsx_ctx* c, int32_t nmu, const double* mu, int32_t col0, int32_t ncol, int32_t la0, int32_t nla,
+                                             const int32_t* ncomp, const int32_t* alpha, const double* strength, const double* shift,
+                                             const int32_t nnode[3], const double* basis, const double* base, const double* nodes,
+                                             const double amplitude[3], const double* obs, const double* weight,
+                                             double* chi2, double* grad, double* hess, double* field_out, const lsx_fit_instrument* inst)
+{
+    if (!inst)
+        return lsx_hip_fit_field_normal(c, nmu, mu, col0, ncol, la0, nla, ncomp, alpha, strength, shift, nnode, basis, base, nodes, amplitude,
+                                        obs, weight, chi2, grad, hess, field_out);
+    return fit_run(c, "lsx_hip_instrument_fit_normal", true, nmu, mu, col0, ncol, la0, nla, ncomp, alpha, strength, shift, nnode, basis, base,
+                   nodes, amplitude, obs, weight, chi2, grad, hess, field_out, inst);
+}
+
+extern "C" int lsx_hip_instrument_fit_chi2(lsx_ctx* c, int32_t nmu, const double* mu, int32_t col0, int32_t ncol, int32_t la0, int32_t nla,
+                                           const int32_t* ncomp, const int32_t* alpha, const double* strength, const double* shift,
+                                           const int32_t nnode[3], const double* basis, const double* base, const double* nodes,
+                                           const double* obs, const double* weight, double* chi2, double* field_out,
+                                           const lsx_fit_instrument* inst)
+{
+    if (!inst)
+        return lsx_hip_fit_field_chi2(c, nmu, mu, col0, ncol, la0, nla, ncomp, alpha, strength, shift, nnode, basis, base, nodes, obs, weight,
+                                      chi2, field_out);
+    return fit_run(c, "lsx_hip_instrument_fit_chi2", false, nmu, mu, col0, ncol, la0, nla, ncomp, alpha, strength, shift, nnode, basis, base,
+                   nodes, nullptr, obs, weight, chi2, nullptr, nullptr, field_out, inst);
 }
 
 extern "C" int lsx_hip_fit_field_step(lsx_ctx* c, int32_t ncol, int32_t P, const double* hess, const double* grad, const double* lambda,

@@ -2,6 +2,7 @@
 // compiler also accepts: lsx_fit.hip runs them in its kernels, lsx_fit_host.cpp on arrays handed over (tests, the sanitizer program).
 //   expand        the field of a column from its nodes
 //   contract      a row of the Jacobian at one data point: the response summed over depth against a basis row
+//   smear         an observed point of the instrument: a pixel's weights against the grid points it reads
 //   residual      the weight and the residual of a data point
 //   lane_sum      a lane's part of a sum over the data points, tree_step one level of the tree that joins the kReduceLanes parts
 //   entry_pair    which sum an entry of the reduction is
@@ -39,6 +40,16 @@ LSXFIT_HD double contract(const double* rf, size_t stride, PB basis, int Ns)
     double j = 0.0;
     for (int k = 0; k < Ns; ++k) j += rf[(size_t)k * stride] * basis[k];
     return j;
+}
+
+// an observed point of the instrument (lsx_fit_instrument): sum_i weight[i] x[i stride], i ascending from 0.0; weight: the pixel's row,
+// x: the first grid point the pixel reads
+template <class PW>
+LSXFIT_HD double smear(PW weight, int width, const double* x, size_t stride)
+{
+    double s = 0.0;
+    for (int i = 0; i < width; ++i) s += weight[i] * x[(size_t)i * stride];
+    return s;
 }
 
 // the weight (null: 1) and the residual of a data point; a point of weight zero has residual zero: its obs does not enter

@@ -1,6 +1,6 @@
 // lsx_fit_host.cpp -- the arithmetic of lsx_fit_dev.h compiled for the CPU, on arrays handed over (tests and the sanitizer program only:
-// `make fithost`, `make fitsan`).  What lsx_fit.hip does in k_fit_jac, k_fit_reduce and k_fit_step, in the kernels' order: the same
-// lanes' parts, the same tree.  Built with -ffp-contract=off.
+// `make fithost`, `make fitsan`, `make fitinstsan`).  What lsx_fit.hip does in k_fit_jac, k_fit_reduce and k_fit_step and
+// lsx_fit_instrument.hip in k_fit_smear, in the kernels' order: the same lanes' parts, the same tree.  Built with -ffp-contract=off.
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -33,6 +33,71 @@ double block_sum(int M, const double* w, const double* x, const double* y)
     return v[0];
 }
 
+// the instrument's rules (include/lsx_hip_fit_instrument.h)
+bool instrument_ok(int32_t nla, int32_t nobs, int32_t width, const int32_t* first, const double* iweight)
+{
+    if (!first || !iweight || nobs < 1 || width < 1 || width > nla) return false;
+    for (int o = 0; o < nobs; ++o)
+        if (first[o] < 0 || first[o] > nla - width) return false;
+    for (size_t i = 0; i < (size_t)nobs * width; ++i)
+        if (!std::isfinite(iweight[i])) return false;
+    return true;
+}
+
+// a row of ns blocks [nla][nmu] -> ns blocks [nobs][nmu], point by point as a lane of k_fit_smear forms it
+void smear_row(int ns, int nla, int nmu, int nobs, int width, const int32_t* first, const double* iweight, const double* in, double* out)
+{
+    for (int d = 0; d < ns * nobs * nmu; ++d) {
+        const int so = d / nmu, m = d - so * nmu;
+        const int s = so / nobs, o = so - s * nobs;
+        out[d] = smear(iweight + (size_t)o * width, width, in + ((size_t)s * nla + first[o]) * nmu + m, (size_t)nmu);
+    }
+}
+
+// the sums of one column; first null: no instrument
+int normal_run(int32_t Ns, int32_t nla, int32_t nmu, const int32_t* nnode, const double* rf, const double* S, const double* obs,
+               const double* weight, const double* basis, int32_t nobs, int32_t width, const int32_t* first, const double* iweight,
+               double* chi2, double* grad, double* hess)
+{
+    const int P = count_params(nnode);
+    const bool normal = grad || hess;
+    if (P < 0 || Ns < 1 || nla < 1 || nmu < 1 || !S || !obs || !chi2 || (normal && (!grad || !hess || !rf || !basis))) return LSX_EINVAL;
+    if (first && !instrument_ok(nla, nobs, width, first, iweight)) return LSX_EINVAL;
+    const int Mg = 4 * nla * nmu, M = first ? 4 * nobs * nmu : Mg;
+    std::vector<double> W((size_t)M), R((size_t)M), J(normal ? (size_t)P * Mg : 0), Ss, Js;
+    if (first) {
+        Ss.resize((size_t)M);
+        smear_row(4, nla, nmu, nobs, width, first, iweight, S, Ss.data());
+        S = Ss.data();
+    }
+    for (int d = 0; d < M; ++d) residual(weight, obs, S, (size_t)d, W[d], R[d]);
+    *chi2 = block_sum(M, W.data(), R.data(), R.data());
+    if (!normal) return LSX_OK;
+    const size_t block = (size_t)Ns * nmu;
+    for (int a = 0, i = 0, j = 0; a < 3; ++a) {
+        for (int n = 0; n < nnode[a]; ++n, ++j)
+            for (int d = 0; d < Mg; ++d) {
+                const int sl = d / nmu, m = d - sl * nmu;
+                J[(size_t)j * Mg + d] = contract(rf + (size_t)i * 4 * nla * block + (size_t)sl * block + m, (size_t)nmu, basis + (size_t)j * Ns, Ns);
+            }
+        i += nnode[a] > 0;
+    }
+    const double* Jr = J.data();
+    if (first) {
+        Js.resize((size_t)P * M);
+        for (int j = 0; j < P; ++j) smear_row(4, nla, nmu, nobs, width, first, iweight, J.data() + (size_t)j * Mg, Js.data() + (size_t)j * M);
+        Jr = Js.data();
+    }
+    for (int e = 0; e < entries(P) - 1; ++e) {
+        int a, b;
+        entry_pair(P, e, a, b);
+        const double sum = block_sum(M, W.data(), Jr + (size_t)a * M, b >= 0 ? Jr + (size_t)b * M : R.data());
+        if (b >= 0) hess[(size_t)a * P + b] = hess[(size_t)b * P + a] = sum;
+        else grad[a] = sum;
+    }
+    return LSX_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -58,31 +123,26 @@ int lsx_fit_host_expand(int32_t Ns, int32_t ncol, const int32_t* nnode, const do
 int lsx_fit_host_normal(int32_t Ns, int32_t nla, int32_t nmu, const int32_t* nnode, const double* rf, const double* S, const double* obs,
                         const double* weight, const double* basis, double* chi2, double* grad, double* hess)
 {
-    const int P = count_params(nnode);
-    const bool normal = grad || hess;
-    if (P < 0 || Ns < 1 || nla < 1 || nmu < 1 || !S || !obs || !chi2 || (normal && (!grad || !hess || !rf || !basis))) return LSX_EINVAL;
-    const int M = 4 * nla * nmu;
-    std::vector<double> W((size_t)M), R((size_t)M), J(normal ? (size_t)P * M : 0);
-    for (int d = 0; d < M; ++d) residual(weight, obs, S, (size_t)d, W[d], R[d]);
-    *chi2 = block_sum(M, W.data(), R.data(), R.data());
-    if (!normal) return LSX_OK;
-    const size_t block = (size_t)Ns * nmu;
-    for (int a = 0, i = 0, j = 0; a < 3; ++a) {
-        for (int n = 0; n < nnode[a]; ++n, ++j)
-            for (int d = 0; d < M; ++d) {
-                const int sl = d / nmu, m = d - sl * nmu;
-                J[(size_t)j * M + d] = contract(rf + (size_t)i * 4 * nla * block + (size_t)sl * block + m, (size_t)nmu, basis + (size_t)j * Ns, Ns);
-            }
-        i += nnode[a] > 0;
-    }
-    for (int e = 0; e < entries(P) - 1; ++e) {
-        int a, b;
-        entry_pair(P, e, a, b);
-        const double sum = block_sum(M, W.data(), J.data() + (size_t)a * M, b >= 0 ? J.data() + (size_t)b * M : R.data());
-        if (b >= 0) hess[(size_t)a * P + b] = hess[(size_t)b * P + a] = sum;
-        else grad[a] = sum;
-    }
+    return normal_run(Ns, nla, nmu, nnode, rf, S, obs, weight, basis, 0, 0, nullptr, nullptr, chi2, grad, hess);
+}
+
+// the instrument on arrays handed over: in [nrow][nla][nmu] -> out [nrow][nobs][nmu]; first [nobs], iweight [nobs][width]
+int lsx_fit_host_smear(int32_t nla, int32_t nmu, int32_t nrow, int32_t nobs, int32_t width, const int32_t* first, const double* iweight,
+                       const double* in, double* out)
+{
+    if (nla < 1 || nmu < 1 || nrow < 1 || !in || !out || !instrument_ok(nla, nobs, width, first, iweight)) return LSX_EINVAL;
+    for (size_t r = 0; r < (size_t)nrow; ++r)
+        smear_row(1, nla, nmu, nobs, width, first, iweight, in + r * nla * nmu, out + r * nobs * nmu);
     return LSX_OK;
+}
+
+// lsx_fit_host_normal through an instrument: obs, weight [4][nobs][nmu]; S and rf on the window's grid as there.  first null: that one.
+int lsx_fit_host_normal_inst(int32_t Ns, int32_t nla, int32_t nmu, const int32_t* nnode, const double* rf, const double* S,
+                             const double* obs, const double* weight, const double* basis, int32_t nobs, int32_t width,
+                             const int32_t* first, const double* iweight, double* chi2, double* grad, double* hess)
+{
+    if (!first && iweight) return LSX_EINVAL;
+    return normal_run(Ns, nla, nmu, nnode, rf, S, obs, weight, basis, nobs, width, first, iweight, chi2, grad, hess);
 }
 
 // lsx_hip_fit_field_step on the CPU; delta [ncol][P] (may be null): the unclamped solution (NaN where status is 1)

@@ -301,7 +301,7 @@ def fit_field_columns(backend, obs, mus, basis, nodes0, nnode, weight=None, base
     backend: anything with fit_field_normal, fit_field_chi2 and fit_field_step as Engine has them (an Engine is one).  obs
     [ncol][4][nla][nmu]; basis [P][Nspace], nnode, nodes0 [ncol][P], weight, base as in Engine.fit_field_normal; lo, hi [P]: bounds
     of the node values; **call: what else the backend's two field calls take (patterns, la0, nla, col0, ncol, amplitudes for the
-    normal equations).  Per iteration and column: the normal equations at the nodes, the damped step, chi2 of the trial; where chi2
+    normal equations; instrument: a fit.Instrument, then obs and weight are [ncol][4][nobs][nmu]).  Per iteration and column: the normal equations at the nodes, the damped step, chi2 of the trial; where chi2
     fell the trial is accepted and lambda /= factor (not below lambda_min), otherwise lambda *= factor.  A column is done when a
     trial moved chi2 by less than tol x the chi2 the column started from (the trial is still accepted if it is lower), when lambda
     passes lambda_max, or at max_iter; a done column is frozen: its nodes no longer move.  This loop compares and scales scalars;

@@ -730,7 +730,34 @@ class Engine:
         return StokesResponse({w: rf[:, i] for i, w in enumerate(names)}, StokesRays(mu, la0, out[:, 0], out[:, 1], out[:, 2], out[:, 3]),
                               np.arange(Ns, dtype=np.int32) if kk is None else kk, mu, la0, {w: float(amps[w]) for w in names})
 
-    def _fit_args(self, who, mus, basis, nnode, nodes, obs, weight, base, patterns, la0, nla, col0, ncol, work_cap_bytes):
+    def _instrument(self, who, instrument, nla):
+        """-> (the C struct of a fit.Instrument, what must outlive the call)"""
+        from . import _capi
+        if not getattr(self.lib, 'has_fit_instrument', False):
+            raise NotImplementedError('%s (%s) does not export lsx_hip_instrument_fit_normal: %s through an instrument is computed by '
+                                      'the HIP library only' % (self.lib.path, self.lib.backend, who))
+        if instrument.nla != nla:
+            raise ValueError('%s: the instrument is made for %d wavelengths, the window has %d' % (who, instrument.nla, nla))
+        first, weight = instrument.first, instrument.weight
+        st = _capi.LsxFitInstrument(instrument.nobs, instrument.width, first.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(weight))
+        return st, (first, weight)
+
+    def apply_instrument(self, x, instrument):
+        """The instrument applied on the device, by the kernel the fit runs (include/lsx_hip_fit_instrument.h,
+        lsx_hip_instrument_apply): x [...][nla][nmu] -> [...][nobs][nmu], e.g. the [ncol][4][nla][nmu] of stokes_rays stacked.  What
+        the fit forms inside for the same numbers, bit for bit.  Does not touch the engine's state."""
+        a = f64(np.asarray(x, dtype=np.float64))
+        if a.ndim < 2:
+            raise ValueError('apply_instrument: x must be [...][nla][nmu]')
+        nla, nmu = a.shape[-2:]
+        st, keep = self._instrument('apply_instrument', instrument, nla)
+        nrow = int(np.prod(a.shape[:-2]))
+        out = np.empty(a.shape[:-2] + (instrument.nobs, nmu), dtype=np.float64)
+        self.lib.check(self.lib.dll.lsx_hip_instrument_apply(self._h, C.byref(st), nla, nmu, nrow, _ptr(a), _ptr(out)))
+        del keep
+        return out
+
+    def _fit_args(self, who, mus, basis, nnode, nodes, obs, weight, base, patterns, la0, nla, col0, ncol, work_cap_bytes, instrument=None):
         from . import zeeman
         if not getattr(self.lib, 'has_fit_field', False):
             raise NotImplementedError('%s (%s) does not export lsx_hip_%s: the field fit is computed by the HIP library only'
@@ -749,7 +776,7 @@ class Engine:
         if bas.shape[0] != int(nn.sum()):
             raise ValueError('%s: basis has %d rows, nnode sums to %d' % (who, bas.shape[0], int(nn.sum())))
         x = f64(np.broadcast_to(np.asarray(nodes, dtype=np.float64), (nc, P)))
-        shape = (nc, 4, max(nla, 0), mu.shape[0])
+        shape = (nc, 4, max(nla, 0) if instrument is None else instrument.nobs, mu.shape[0])
         ob = f64(np.asarray(obs, dtype=np.float64).reshape(shape))
         wt = None if weight is None else f64(np.broadcast_to(np.asarray(weight, dtype=np.float64), shape))
         bs = None if base is None else f64(np.broadcast_to(np.asarray(base, dtype=np.float64), (nc, 3, Ns)))
@@ -761,33 +788,46 @@ class Engine:
         return head, keep, _ptr(ob), None if wt is None else _ptr(wt), nc, P, Ns
 
     def fit_field_normal(self, mus, basis, nnode, nodes, obs, weight=None, base=None, patterns=None, la0=0, nla=None, col0=0, ncol=None,
-                         amplitudes=None, work_cap_bytes=None):
+                         amplitudes=None, work_cap_bytes=None, instrument=None):
         """chi2 and the normal equations of the fit of the field vector to observed Stokes profiles at `nodes`
         (include/lsx_hip_fit.h, lsx_hip_fit_field_normal): the field of a column is base_p + sum_n nodes[p][n] basis_p[n] for p of
         B, gammaB, chiB; nnode: the three node counts (0: not fitted); basis [P][Nspace], the rows of B first; nodes [ncol][P];
         base [ncol][3][Nspace] or None; obs, weight [ncol][4][nla][nmu] (weight None: 1).  mus, patterns, la0, nla, col0, ncol as in
         stokes_rays; amplitudes as in stokes_response.  The response never leaves the device.  Read-only.
+        instrument: a fit.Instrument over the window's nla wavelengths (include/lsx_hip_fit_instrument.h): obs and weight are
+        [ncol][4][nobs][nmu], the Stokes vector and the Jacobian are smeared and sampled on the device before the sums; None: as ever.
         -> fit.FieldNormal (.chi2, .grad, .hess, .field).  Only the HIP library computes it."""
         from .fit import FieldNormal
         head, keep, ob, wt, nc, P, Ns = self._fit_args('fit_field_normal', mus, basis, nnode, nodes, obs, weight, base, patterns, la0, nla,
-                                                       col0, ncol, work_cap_bytes)
+                                                       col0, ncol, work_cap_bytes, instrument)
         amps = dict(StokesResponse.DEFAULT_AMPLITUDES)
         amps.update(amplitudes or {})
         amp = f64(np.array([amps[w] for w in StokesResponse.PARAMETERS], dtype=np.float64))
         chi2, grad, hess = np.empty(nc), np.empty((nc, P)), np.empty((nc, P, P))
         field = np.empty((nc, 3, Ns))
-        self.lib.check(self.lib.dll.lsx_hip_fit_field_normal(*head, _ptr(amp), ob, wt, _ptr(chi2), _ptr(grad), _ptr(hess), _ptr(field)))
+        if instrument is None:
+            self.lib.check(self.lib.dll.lsx_hip_fit_field_normal(*head, _ptr(amp), ob, wt, _ptr(chi2), _ptr(grad), _ptr(hess), _ptr(field)))
+        else:
+            st, keep_i = self._instrument('fit_field_normal', instrument, head[6])
+            self.lib.check(self.lib.dll.lsx_hip_instrument_fit_normal(*head, _ptr(amp), ob, wt, _ptr(chi2), _ptr(grad), _ptr(hess),
+                                                                      _ptr(field), C.byref(st)))
+            del keep_i
         del keep
         return FieldNormal(chi2, grad, hess, field)
 
     def fit_field_chi2(self, mus, basis, nnode, nodes, obs, weight=None, base=None, patterns=None, la0=0, nla=None, col0=0, ncol=None,
-                       work_cap_bytes=None):
+                       work_cap_bytes=None, instrument=None):
         """chi2 of the field expanded from `nodes` (lsx_hip_fit_field_chi2): one Stokes pass and the reduction of fit_field_normal --
         its chi2, bit for bit.  Arguments as fit_field_normal.  -> (chi2 [ncol], field [ncol][3][Nspace])."""
         head, keep, ob, wt, nc, P, Ns = self._fit_args('fit_field_chi2', mus, basis, nnode, nodes, obs, weight, base, patterns, la0, nla,
-                                                       col0, ncol, work_cap_bytes)
+                                                       col0, ncol, work_cap_bytes, instrument)
         chi2, field = np.empty(nc), np.empty((nc, 3, Ns))
-        self.lib.check(self.lib.dll.lsx_hip_fit_field_chi2(*head, ob, wt, _ptr(chi2), _ptr(field)))
+        if instrument is None:
+            self.lib.check(self.lib.dll.lsx_hip_fit_field_chi2(*head, ob, wt, _ptr(chi2), _ptr(field)))
+        else:
+            st, keep_i = self._instrument('fit_field_chi2', instrument, head[6])
+            self.lib.check(self.lib.dll.lsx_hip_instrument_fit_chi2(*head, ob, wt, _ptr(chi2), _ptr(field), C.byref(st)))
+            del keep_i
         del keep
         return chi2, field
 

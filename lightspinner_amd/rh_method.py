@@ -504,7 +504,7 @@ class Context:
         pick = (lambda a: a[0, 0]) if scalar else (lambda a: a[0])
         return DepthRays(r.mus, r.la0, **{w: pick(getattr(r, w)) for w in DepthRays.FIELDS})
 
-    def compute_stokes(self, mus, B, gammaB, chiB, transition=None, la0=0, nla=None):
+    def compute_stokes(self, mus, B, gammaB, chiB, transition=None, la0=0, nla=None, instrument=None):
         """Emergent Stokes spectra I, Q, U, V in a magnetic field (Zeeman effect) by the field-free method: these populations and
         this J, one polarised formal solution (DELO-linear) along the rays with direction cosines `mus`.  B [T], gammaB, chiB [rad]:
         [Nspace] or scalars -- strength, inclination against the vertical, azimuth; +Q lies along the projection of the vertical
@@ -512,6 +512,7 @@ class Context:
         The Zeeman patterns come from the context's own line models (zeeman.zeeman_components: gLandeEff, or LS coupling from the
         levels' J, L, S); a line without either stays unpolarised.  transition: one of the context's transitions (the object, or its
         place in [t for atom in activeAtoms for t in atom.trans]) selects that transition's own window, as in compute_depth_rays.
+        instrument: a fit.Instrument over the window's wavelengths: the spectra as it sees them, [nobs][nmu] (Engine.apply_instrument).
         -> an object with .I .Q .U .V, each [nla][nmu] ([nla] for a float mu), .mus, .la0.  Nothing of the context changes."""
         from . import zeeman
         from .problem import StokesRays
@@ -525,6 +526,9 @@ class Context:
         scalar = np.ndim(mus) == 0
         r = self._engine.stokes_rays(np.atleast_1d(np.asarray(mus, dtype=np.float64)), B, gammaB, chiB, patterns=patterns, la0=la0, nla=nla)
         pick = (lambda a: a[0, :, 0]) if scalar else (lambda a: a[0])
+        if instrument is not None:
+            seen = self._engine.apply_instrument(np.stack([getattr(r, w) for w in StokesRays.FIELDS], axis=1), instrument)
+            return StokesRays(r.mus, r.la0, *(pick(seen[:, i]) for i in range(4)))
         return StokesRays(r.mus, r.la0, *(pick(getattr(r, w)) for w in StokesRays.FIELDS))
 
     def compute_stokes_response(self, mus, B, gammaB, chiB, transition=None, la0=0, nla=None, parameters=('B', 'gammaB', 'chiB'),
@@ -553,13 +557,14 @@ class Context:
         return StokesResponse({w: (a[0, ..., 0] if scalar else a[0]) for w, a in r.rf.items()}, stokes, r.ks, r.mus, r.la0, r.amplitudes)
 
     def fit_field(self, mus, obs, transition=None, basis=None, start=None, nnode=None, weight=None, base=None, la0=0, nla=None,
-                  amplitudes=None, **loop):
+                  amplitudes=None, instrument=None, **loop):
         """Fit the magnetic field vector to observed Stokes profiles obs [4][nla][nmu] ([4][nla] for a float mu) by the field-free
         method: these populations and this J, Levenberg-Marquardt on the node values of field_p = base_p + sum_n x[p][n] basis_p[n]
         (drivers.fit_field_columns on the context's engine; include/lsx_hip_fit.h).  basis [P][Nspace] with nnode = the node counts of
         (B, gammaB, chiB), or a dict from those names to row sets (fit.hat_basis makes them); start: the first node values [P];
         weight as obs or None; base [3][Nspace] or None; mus, transition, la0, nla and the Zeeman patterns as in compute_stokes;
-        amplitudes as in compute_stokes_response; **loop: lo, hi, lambda0, factor, lambda_min, lambda_max, tol, max_iter, log.
+        amplitudes as in compute_stokes_response; instrument: a fit.Instrument over the window's wavelengths, then obs and weight are
+        [4][nobs][nmu]; **loop: lo, hi, lambda0, factor, lambda_min, lambda_max, tol, max_iter, log.
         -> fit.FieldFit without the column axis.  Nothing of the context changes."""
         from . import zeeman
         from .drivers import fit_field_columns
@@ -577,10 +582,13 @@ class Context:
         patterns = [zeeman.zeeman_components(t.transModel) for a in self.activeAtoms for t in a.trans if t.isLine]
         mu = np.atleast_1d(np.asarray(mus, dtype=np.float64))
         nla_ = self._engine.problem.Nspect - int(la0) if nla is None else int(nla)
-        shape = (1, 4, nla_, mu.shape[0])
+        npix = nla_ if instrument is None else instrument.nobs
+        shape = (1, 4, npix, mu.shape[0])
+        if instrument is not None:
+            loop['instrument'] = instrument
         r = fit_field_columns(self._engine, np.asarray(obs, dtype=np.float64).reshape(shape), mu, basis, np.asarray(start)[None, :], nnode,
                               weight=None if weight is None else np.broadcast_to(np.asarray(weight, dtype=np.float64).reshape(
-                                  (1, 4, nla_, -1) if np.ndim(weight) else ()), shape),
+                                  (1, 4, npix, -1) if np.ndim(weight) else ()), shape),
                               base=None if base is None else np.asarray(base, dtype=np.float64)[None], patterns=patterns, la0=la0, nla=nla_,
                               amplitudes=amplitudes, **loop)
         return FieldFit(r.nodes[0], r.field[0], r.chi2[0], r.history[:, 0], r.lam[0], r.iterations[0], r.status[0], r.nnode)
