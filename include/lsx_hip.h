@@ -84,5 +84,6 @@ int lsx_hip_poison_lds(int32_t device, int32_t rounds);
 #include "lsx_hip_stokes.h"
 #include "lsx_hip_stokes_response.h"
 #include "lsx_hip_fit.h"
+#include "lsx_hip_stokes_velocity.h"
 
 #endif /* LSX_HIP_H */

@@ -285,6 +285,22 @@ class LsxLibrary:
             d.lsx_hip_instrument_fit_chi2.restype = C.c_int
             d.lsx_hip_instrument_apply.argtypes = [C.c_void_p, inst, C.c_int32, C.c_int32, C.c_int32, _dp, _dp]
             d.lsx_hip_instrument_apply.restype = C.c_int
+        self.has_stokes_velocity = hasattr(d, 'lsx_hip_velocity_stokes_rays')      # include/lsx_hip_stokes_velocity.h
+        if self.has_stokes_velocity:
+            ip32 = C.POINTER(C.c_int32)
+            inst = C.POINTER(LsxFitInstrument)
+            d.lsx_hip_velocity_stokes_rays.argtypes = [C.c_void_p, C.c_int32, _dp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp,
+                                                       ip32, ip32, _dp, _dp, _dp, C.c_size_t, _dp]
+            d.lsx_hip_velocity_stokes_rays.restype = C.c_int
+            d.lsx_hip_velocity_response_stokes.argtypes = [C.c_void_p, C.c_int32, _dp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, _dp,
+                                                           _dp, ip32, ip32, _dp, _dp, C.c_uint32, _dp, C.c_int32, ip32, _dp, C.c_size_t, _dp,
+                                                           C.c_size_t, _dp]
+            d.lsx_hip_velocity_response_stokes.restype = C.c_int
+            head = [C.c_void_p, C.c_int32, _dp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, ip32, ip32, _dp, _dp, ip32, _dp, _dp, _dp]
+            d.lsx_hip_velocity_fit_normal.argtypes = head + [_dp, _dp, _dp, _dp, _dp, _dp, _dp, inst]
+            d.lsx_hip_velocity_fit_normal.restype = C.c_int
+            d.lsx_hip_velocity_fit_chi2.argtypes = head + [_dp, _dp, _dp, _dp, inst]
+            d.lsx_hip_velocity_fit_chi2.restype = C.c_int
         self.has_background = hasattr(d, 'lsx_hip_background')         # include/lsx_hip_background.h
         if self.has_background:
             ip32 = C.POINTER(C.c_int32)

@@ -29,7 +29,8 @@ protected:
 };
 // What a Stokes pass is asked for, as lsx_hip_stokes_rays takes it (include/lsx_hip_stokes.h): angles, columns, window of the merged
 // grid, the field of the call's columns ([ncol][Nspace] each) and the Zeeman patterns of the lines.  The entries build it from their
-// arguments, in this order; lsx_fit.hip builds one per group of columns
+// arguments, in this order; lsx_fit.hip builds one per group of columns.  vlos (include/lsx_hip_stokes_velocity.h): null, or the
+// line-of-sight velocity of the call's columns [ncol][Nspace], which stands in the place of the context's in this pass alone
 struct StokesCall {
     int32_t nmu;
     const double* mu;
@@ -37,12 +38,15 @@ struct StokesCall {
     const double *B, *gammaB, *chiB;
     const int32_t *ncomp, *alpha;
     const double *strength, *shift;
+    const double* vlos = nullptr;
+    int nfield() const { return vlos ? 4 : 3; }        // the arrays of [ncol][Nspace] a pass uploads
 };
-// the bodies of lsx_hip_stokes_rays (lsx_stokes.hip) and lsx_hip_response_stokes (lsx_stokes_response.hip); `who` heads the messages
+// the bodies of lsx_hip_stokes_rays (lsx_stokes.hip) and lsx_hip_response_stokes (lsx_stokes_response.hip); `who` heads the messages.
+// amplitude: [3], or [4] where the call has a velocity (bit 8 of params, the response to vlos, is accepted only then)
 int stokes_rays_run(lsx_ctx* c, const char* who, const StokesCall& s, double* out, size_t nbytes, PassSink* sink);
-int response_stokes_check(lsx_ctx* c, const char* who, const StokesCall& s, uint32_t params, const double amplitude[3], int32_t nk,
+int response_stokes_check(lsx_ctx* c, const char* who, const StokesCall& s, uint32_t params, const double* amplitude, int32_t nk,
                           const int32_t* ks);
-int response_stokes_run(lsx_ctx* c, const char* who, const StokesCall& s, uint32_t params, const double amplitude[3], int32_t nk,
+int response_stokes_run(lsx_ctx* c, const char* who, const StokesCall& s, uint32_t params, const double* amplitude, int32_t nk,
                         const int32_t* ks, double* rf, size_t rf_bytes, const size_t* stokes_bytes, PassSink* sink);
 // What the two passes share on the host (lsx_stokes.hip).  The argument rules every Stokes call answers to, in the order
 // lsx_hip_stokes_rays always tested them, in two halves because that entry tests its byte count between them: what the call says
@@ -52,7 +56,8 @@ int stokes_check_call(const lsx_ctx* c, const char* who, const StokesCall& s);
 int stokes_check_state(const lsx_ctx* c, const char* who, const StokesCall& s);
 // the patterns of the lines that are active somewhere in the window, packed for the device (lsx_stokes_prep.h, pack_patterns)
 int stokes_patterns(const lsx_ctx* c, const char* who, const StokesCall& s, std::vector<int32_t>& pat_line, std::vector<double>& pat_tab);
-// the field of a pass: columns [b0, b0 + nb) of the call's three arrays to d_field, nb * Nspace doubles each, that far apart
+// the field of a pass: columns [b0, b0 + nb) of the call's three arrays (and of its velocity, if it has one, as the fourth) to
+// d_field, nb * Nspace doubles each, that far apart
 int stokes_upload_field(lsx_ctx* c, const StokesCall& s, size_t b0, size_t nb, double* d_field);
 
 // The device buffers that grow with the calls: the work arrays of the passes under a cap, and the tables of a call.  One per purpose;

@@ -206,8 +206,10 @@ struct SumPass final : PassSink {
     }
 };
 
-// both entries: normal (grad, hess, amplitude given) or chi2 alone
-int fit_run(lsx_ctx* c, const char* who, bool normal, int32_t nmu, const double* mu, int32_t col0, int32_t ncol, int32_t la0, int32_t nla,
+// both entries: normal (grad, hess, amplitude given) or chi2 alone.  nq: the quantities of the parameterisation -- 3 (B, gammaB, chiB:
+// include/lsx_hip_fit.h) or 4 (with vlos: include/lsx_hip_stokes_velocity.h; the passes are then handed the expanded velocity);
+// nnode, amplitude hold nq entries, base and field_out nq rows a column
+int fit_run(lsx_ctx* c, const char* who, bool normal, int nq, int32_t nmu, const double* mu, int32_t col0, int32_t ncol, int32_t la0, int32_t nla,
             const int32_t* ncomp, const int32_t* alpha, const double* strength, const double* shift, const int32_t* nnode,
             const double* basis, const double* base, const double* nodes, const double* amplitude, const double* obs,
             const double* weight, double* chi2, double* grad, double* hess, double* field_out, const lsx_fit_instrument* inst)
@@ -221,7 +223,7 @@ int fit_run(lsx_ctx* c, const char* who, bool normal, int32_t nmu, const double*
     if (rc) return rc;
     if (inst && (rc = fit_instrument_check(who, inst, nla, nmu, 4))) return rc;
     int64_t Psum = 0;
-    for (int a = 0; a < 3; ++a) {
+    for (int a = 0; a < nq; ++a) {
         if (nnode[a] < 0) return fail(LSX_EINVAL, "%s: nnode[%d] = %d is negative", who, a, (int)nnode[a]);
         Psum += nnode[a];
     }
@@ -234,9 +236,9 @@ int fit_run(lsx_ctx* c, const char* who, bool normal, int32_t nmu, const double*
     size_t bad = 0;
     if (!all_finite(basis, (size_t)P * Ns, bad))
         return fail(LSX_EINVAL, "%s: basis[%zu][%zu] is not finite", who, bad / Ns, bad % Ns);
-    if (base && !all_finite(base, NC * 3 * Ns, bad))
-        return fail(LSX_EINVAL, "%s: base of column %d, parameter %zu, depth %zu is not finite", who, col0 + (int)(bad / (3 * (size_t)Ns)),
-                    bad / Ns % 3, bad % Ns);
+    if (base && !all_finite(base, NC * nq * Ns, bad))
+        return fail(LSX_EINVAL, "%s: base of column %d, parameter %zu, depth %zu is not finite", who, col0 + (int)(bad / (nq * (size_t)Ns)),
+                    bad / Ns % nq, bad % Ns);
     if (!all_finite(nodes, NC * P, bad)) return fail(LSX_EINVAL, "%s: node %zu of column %d is not finite", who, bad % P, col0 + (int)(bad / P));
     if (!all_finite(obs, NC * M, bad)) return fail(LSX_EINVAL, "%s: obs of column %d is not finite (entry %zu)", who, col0 + (int)(bad / M), bad % M);
     if (weight) {
@@ -247,27 +249,32 @@ int fit_run(lsx_ctx* c, const char* who, bool normal, int32_t nmu, const double*
                 return fail(LSX_EINVAL, "%s: weight of column %d is negative (entry %zu): %g", who, col0 + (int)(i / M), i % M, weight[i]);
     }
     // the expansion, in this one place: what is checked below is what the passes are handed
-    std::vector<double> fld(3 * NC * Ns);
-    double* const F[3] = {fld.data(), fld.data() + NC * Ns, fld.data() + 2 * NC * Ns};
-    int row0[3] = {0, nnode[0], nnode[0] + nnode[1]};
+    constexpr int kQ = lsxst::kMaxResponseParams;
+    std::vector<double> fld((size_t)nq * NC * Ns);
+    double* F[kQ] = {nullptr, nullptr, nullptr, nullptr};
+    int row0[kQ] = {0, 0, 0, 0};
+    for (int a = 0; a < nq; ++a) {
+        F[a] = fld.data() + (size_t)a * NC * Ns;
+        row0[a] = a ? row0[a - 1] + nnode[a - 1] : 0;
+    }
     for (size_t q = 0; q < NC; ++q)
-        for (int a = 0; a < 3; ++a)
+        for (int a = 0; a < nq; ++a)
             for (int k = 0; k < Ns; ++k)
-                F[a][q * Ns + k] = lsxfit::expand(base ? base[(q * 3 + a) * Ns + k] : 0.0, nnode[a], nodes + q * P + row0[a],
+                F[a][q * Ns + k] = lsxfit::expand(base ? base[(q * nq + a) * Ns + k] : 0.0, nnode[a], nodes + q * P + row0[a],
                                                   basis + (size_t)row0[a] * Ns, (size_t)Ns, (size_t)k);
     uint32_t params = 0;
-    for (int a = 0; a < 3; ++a) params |= nnode[a] > 0 ? 1u << a : 0u;
+    for (int a = 0; a < nq; ++a) params |= nnode[a] > 0 ? 1u << a : 0u;
     // what the passes are asked for columns [g0, g0 + ng) of the fit's
     const auto call = [&](size_t g0, size_t ng) {
         return StokesCall{nmu, mu, col0 + (int32_t)g0, (int32_t)ng, la0, nla, F[0] + g0 * Ns, F[1] + g0 * Ns, F[2] + g0 * Ns,
-                          ncomp, alpha, strength, shift};
+                          ncomp, alpha, strength, shift, nq > 3 ? F[3] + g0 * Ns : nullptr};
     };
     // chi2 alone: the response's rules without an amplitude's (the Stokes pass's rules are their first part, in its order)
-    static const double unit_amp[3] = {0.0, 1.0, 1.0};
+    static const double unit_amp[kQ] = {0.0, 1.0, 1.0, 1.0};
     if ((rc = response_stokes_check(c, who, call(0, NC), normal ? params : 2u, normal ? amplitude : unit_amp, 0, nullptr))) return rc;
     if (field_out)
         for (size_t q = 0; q < NC; ++q)
-            for (int a = 0; a < 3; ++a) std::copy(F[a] + q * Ns, F[a] + (q + 1) * Ns, field_out + (q * 3 + a) * Ns);
+            for (int a = 0; a < nq; ++a) std::copy(F[a] + q * Ns, F[a] + (q + 1) * Ns, field_out + (q * nq + a) * Ns);
 
     // ---- groups of columns under the fit's cap ----
     HIPCHK(hipSetDevice(c->device));
@@ -297,7 +304,7 @@ int fit_run(lsx_ctx* c, const char* who, bool normal, int32_t nmu, const double*
 
     FitParams p{};
     p.Ns = Ns; p.nla = nla; p.nmu = nmu; p.M = (int32_t)M; p.P = P;
-    int par[3] = {0, 0, 0};
+    int par[kQ] = {0, 0, 0, 0};
     p.npar = lsxst::response_params(params, par);
     for (int i = 0, j = 0; i < p.npar; ++i)
         for (int n = 0; n < nnode[par[i]]; ++n) p.row_par[j++] = (int8_t)i;
@@ -350,7 +357,7 @@ extern "C" int lsx_hip_fit_field_normal(lsx_ctx* c, int32_t nmu, const double* m
                                         const double amplitude[3], const double* obs, const double* weight,
                                         double* chi2, double* grad, double* hess, double* field_out)
 {
-    return fit_run(c, "lsx_hip_fit_field_normal", true, nmu, mu, col0, ncol, la0, nla, ncomp, alpha, strength, shift, nnode, basis, base,
+    return fit_run(c, "lsx_hip_fit_field_normal", true, 3, nmu, mu, col0, ncol, la0, nla, ncomp, alpha, strength, shift, nnode, basis, base,
                    nodes, amplitude, obs, weight, chi2, grad, hess, field_out, nullptr);
 }
 
@@ -359,7 +366,7 @@ extern "C" int lsx_hip_fit_field_chi2(lsx_ctx* c, int32_t nmu, const double* mu,
                                       const int32_t nnode[3], const double* basis, const double* base, const double* nodes,
                                       const double* obs, const double* weight, double* chi2, double* field_out)
 {
-    return fit_run(c, "lsx_hip_fit_field_chi2", false, nmu, mu, col0, ncol, la0, nla, ncomp, alpha, strength, shift, nnode, basis, base, nodes,
+    return fit_run(c, "lsx_hip_fit_field_chi2", false, 3, nmu, mu, col0, ncol, la0, nla, ncomp, alpha, strength, shift, nnode, basis, base, nodes,
                    nullptr, obs, weight, chi2, nullptr, nullptr, field_out, nullptr);
 }
 
@@ -373,7 +380,7 @@ extern "C" int lsx_hip_instrument_fit_normal(lsx_ctx* c, int32_t nmu, const doub
     if (!inst)
         return lsx_hip_fit_field_normal(c, nmu, mu, col0, ncol, la0, nla, ncomp, alpha, strength, shift, nnode, basis, base, nodes, amplitude,
                                         obs, weight, chi2, grad, hess, field_out);
-    return fit_run(c, "lsx_hip_instrument_fit_normal", true, nmu, mu, col0, ncol, la0, nla, ncomp, alpha, strength, shift, nnode, basis, base,
+    return fit_run(c, "lsx_hip_instrument_fit_normal", true, 3, nmu, mu, col0, ncol, la0, nla, ncomp, alpha, strength, shift, nnode, basis, base,
                    nodes, amplitude, obs, weight, chi2, grad, hess, field_out, inst);
 }
 
@@ -386,8 +393,29 @@ extern "C" int lsx_hip_instrument_fit_chi2(lsx_ctx* c, int32_t nmu, const double
     if (!inst)
         return lsx_hip_fit_field_chi2(c, nmu, mu, col0, ncol, la0, nla, ncomp, alpha, strength, shift, nnode, basis, base, nodes, obs, weight,
                                       chi2, field_out);
-    return fit_run(c, "lsx_hip_instrument_fit_chi2", false, nmu, mu, col0, ncol, la0, nla, ncomp, alpha, strength, shift, nnode, basis, base,
+    return fit_run(c, "lsx_hip_instrument_fit_chi2", false, 3, nmu, mu, col0, ncol, la0, nla, ncomp, alpha, strength, shift, nnode, basis, base,
                    nodes, nullptr, obs, weight, chi2, nullptr, nullptr, field_out, inst);
+}
+
+// with four quantities (include/lsx_hip_stokes_velocity.h): the velocity is a row of the expanded field like the others
+extern "C" int lsx_hip_velocity_fit_normal(lsx_ctx* c, int32_t nmu, const double* mu, int32_t col0, int32_t ncol, int32_t la0, int32_t nla,
+                                           const int32_t* ncomp, const int32_t* alpha, const double* strength, const double* shift,
+                                           const int32_t nnode[4], const double* basis, const double* base, const double* nodes,
+                                           const double amplitude[4], const double* obs, const double* weight,
+                                           double* chi2, double* grad, double* hess, double* field_out, const lsx_fit_instrument* inst)
+{
+    return fit_run(c, "lsx_hip_velocity_fit_normal", true, 4, nmu, mu, col0, ncol, la0, nla, ncomp, alpha, strength, shift, nnode, basis, base,
+                   nodes, amplitude, obs, weight, chi2, grad, hess, field_out, inst);
+}
+
+extern "C" int lsx_hip_velocity_fit_chi2(lsx_ctx* c, int32_t nmu, const double* mu, int32_t col0, int32_t ncol, int32_t la0, int32_t nla,
+                                         const int32_t* ncomp, const int32_t* alpha, const double* strength, const double* shift,
+                                         const int32_t nnode[4], const double* basis, const double* base, const double* nodes,
+                                         const double* obs, const double* weight, double* chi2, double* field_out,
+                                         const lsx_fit_instrument* inst)
+{
+    return fit_run(c, "lsx_hip_velocity_fit_chi2", false, 4, nmu, mu, col0, ncol, la0, nla, ncomp, alpha, strength, shift, nnode, basis, base, nodes,
+                   nullptr, obs, weight, chi2, nullptr, nullptr, field_out, inst);
 }
 
 extern "C" int lsx_hip_fit_field_step(lsx_ctx* c, int32_t ncol, int32_t P, const double* hess, const double* grad, const double* lambda,

@@ -12,11 +12,12 @@ using namespace lsxfit;
 
 namespace {
 
-int count_params(const int32_t* nnode)
+// nq: the quantities of the parameterisation, 3 (B, gammaB, chiB) or 4 (with vlos: include/lsx_hip_stokes_velocity.h)
+int count_params(const int32_t* nnode, int nq = 3)
 {
     if (!nnode) return -1;
     int64_t P = 0;
-    for (int a = 0; a < 3; ++a) {
+    for (int a = 0; a < nq; ++a) {
         if (nnode[a] < 0) return -1;
         P += nnode[a];
     }
@@ -55,11 +56,11 @@ void smear_row(int ns, int nla, int nmu, int nobs, int width, const int32_t* fir
 }
 
 // the sums of one column; first null: no instrument
-int normal_run(int32_t Ns, int32_t nla, int32_t nmu, const int32_t* nnode, const double* rf, const double* S, const double* obs,
+int normal_run(int nq, int32_t Ns, int32_t nla, int32_t nmu, const int32_t* nnode, const double* rf, const double* S, const double* obs,
                const double* weight, const double* basis, int32_t nobs, int32_t width, const int32_t* first, const double* iweight,
                double* chi2, double* grad, double* hess)
 {
-    const int P = count_params(nnode);
+    const int P = count_params(nnode, nq);
     const bool normal = grad || hess;
     if (P < 0 || Ns < 1 || nla < 1 || nmu < 1 || !S || !obs || !chi2 || (normal && (!grad || !hess || !rf || !basis))) return LSX_EINVAL;
     if (first && !instrument_ok(nla, nobs, width, first, iweight)) return LSX_EINVAL;
@@ -74,7 +75,7 @@ int normal_run(int32_t Ns, int32_t nla, int32_t nmu, const int32_t* nnode, const
     *chi2 = block_sum(M, W.data(), R.data(), R.data());
     if (!normal) return LSX_OK;
     const size_t block = (size_t)Ns * nmu;
-    for (int a = 0, i = 0, j = 0; a < 3; ++a) {
+    for (int a = 0, i = 0, j = 0; a < nq; ++a) {
         for (int n = 0; n < nnode[a]; ++n, ++j)
             for (int d = 0; d < Mg; ++d) {
                 const int sl = d / nmu, m = d - sl * nmu;
@@ -102,19 +103,33 @@ int normal_run(int32_t Ns, int32_t nla, int32_t nmu, const int32_t* nnode, const
 
 extern "C" {
 
+static int expand_run(int nq, int32_t Ns, int32_t ncol, const int32_t* nnode, const double* basis, const double* base, const double* nodes,
+                      double* field)
+{
+    const int P = count_params(nnode, nq);
+    if (P < 0 || Ns < 1 || ncol < 1 || !basis || !nodes || !field) return LSX_EINVAL;
+    int row0[4] = {0, 0, 0, 0};
+    for (int a = 1; a < nq; ++a) row0[a] = row0[a - 1] + nnode[a - 1];
+    for (size_t q = 0; q < (size_t)ncol; ++q)
+        for (int a = 0; a < nq; ++a)
+            for (int k = 0; k < Ns; ++k)
+                field[(q * nq + a) * Ns + k] = expand(base ? base[(q * nq + a) * Ns + k] : 0.0, nnode[a], nodes + q * P + row0[a],
+                                                      basis + (size_t)row0[a] * Ns, (size_t)Ns, (size_t)k);
+    return LSX_OK;
+}
+
 // the field of ncol columns from their nodes: basis [P][Ns], base [ncol][3][Ns] or null, nodes [ncol][P] -> field [ncol][3][Ns]
 int lsx_fit_host_expand(int32_t Ns, int32_t ncol, const int32_t* nnode, const double* basis, const double* base, const double* nodes,
                         double* field)
 {
-    const int P = count_params(nnode);
-    if (P < 0 || Ns < 1 || ncol < 1 || !basis || !nodes || !field) return LSX_EINVAL;
-    const int row0[3] = {0, nnode[0], nnode[0] + nnode[1]};
-    for (size_t q = 0; q < (size_t)ncol; ++q)
-        for (int a = 0; a < 3; ++a)
-            for (int k = 0; k < Ns; ++k)
-                field[(q * 3 + a) * Ns + k] = expand(base ? base[(q * 3 + a) * Ns + k] : 0.0, nnode[a], nodes + q * P + row0[a],
-                                                     basis + (size_t)row0[a] * Ns, (size_t)Ns, (size_t)k);
-    return LSX_OK;
+    return expand_run(3, Ns, ncol, nnode, basis, base, nodes, field);
+}
+
+// ... with four quantities (include/lsx_hip_stokes_velocity.h): nnode[4], base and field [ncol][4][Ns], the velocity the fourth row
+int lsx_fit_host_expand4(int32_t Ns, int32_t ncol, const int32_t* nnode, const double* basis, const double* base, const double* nodes,
+                         double* field)
+{
+    return expand_run(4, Ns, ncol, nnode, basis, base, nodes, field);
 }
 
 // One column's sums from its response and its Stokes vector: rf [npar][4][nla][Ns][nmu] (npar: the parameters with nodes, in the order
@@ -123,7 +138,17 @@ int lsx_fit_host_expand(int32_t Ns, int32_t ncol, const int32_t* nnode, const do
 int lsx_fit_host_normal(int32_t Ns, int32_t nla, int32_t nmu, const int32_t* nnode, const double* rf, const double* S, const double* obs,
                         const double* weight, const double* basis, double* chi2, double* grad, double* hess)
 {
-    return normal_run(Ns, nla, nmu, nnode, rf, S, obs, weight, basis, 0, 0, nullptr, nullptr, chi2, grad, hess);
+    return normal_run(3, Ns, nla, nmu, nnode, rf, S, obs, weight, basis, 0, 0, nullptr, nullptr, chi2, grad, hess);
+}
+
+// lsx_fit_host_normal_inst with four quantities: nnode[4], rf [npar][4][nla][Ns][nmu] in the order B, gammaB, chiB, vlos.  first null
+// (then iweight must be null too): no instrument
+int lsx_fit_host_normal4(int32_t Ns, int32_t nla, int32_t nmu, const int32_t* nnode, const double* rf, const double* S,
+                         const double* obs, const double* weight, const double* basis, int32_t nobs, int32_t width,
+                         const int32_t* first, const double* iweight, double* chi2, double* grad, double* hess)
+{
+    if (!first && iweight) return LSX_EINVAL;
+    return normal_run(4, Ns, nla, nmu, nnode, rf, S, obs, weight, basis, nobs, width, first, iweight, chi2, grad, hess);
 }
 
 // the instrument on arrays handed over: in [nrow][nla][nmu] -> out [nrow][nobs][nmu]; first [nobs], iweight [nobs][width]
@@ -142,7 +167,7 @@ int lsx_fit_host_normal_inst(int32_t Ns, int32_t nla, int32_t nmu, const int32_t
                              const int32_t* first, const double* iweight, double* chi2, double* grad, double* hess)
 {
     if (!first && iweight) return LSX_EINVAL;
-    return normal_run(Ns, nla, nmu, nnode, rf, S, obs, weight, basis, nobs, width, first, iweight, chi2, grad, hess);
+    return normal_run(3, Ns, nla, nmu, nnode, rf, S, obs, weight, basis, nobs, width, first, iweight, chi2, grad, hess);
 }
 
 // lsx_hip_fit_field_step on the CPU; delta [ncol][P] (may be null): the unclamped solution (NaN where status is 1)

@@ -44,7 +44,7 @@ struct StokesParams {
     const int32_t* bnd;         // the radiation boundary (lsx_dev.h, the boundary store), or null
     const int32_t* pat_line;    // [Nlines][2]: components of the line's pattern (0: unpolarised), the first one's place in pat_tab
     const double* pat_tab;      // [ntab]: per component (shift, weight of phi_-1, of phi_0, of phi_+1)
-    const double* field;        // B, gammaB, chiB: [3][launch columns][Ns], fstride apart
+    const double* field;        // B, gammaB, chiB (and, in a call with a velocity, vlos): [3 or 4][launch columns][Ns], fstride apart
     double* out;                // [launch column][4][nla][nmu]
 };
 
@@ -53,7 +53,9 @@ struct W2Dev {                  // the linear rule's weights as the other final 
     __device__ __forceinline__ void operator()(double dtau, double& w0, double& w1) const { w2(dtau, w0, w1, etab); }
 };
 
-template <int NM>
+// VEL: the call has a velocity (include/lsx_hip_stokes_velocity.h) -- the fourth array of p.field in the place of the context's vlos,
+// and every line formed from the kept broadening arrays: the context's profile store is not read.  VEL = false is the kernel as it was.
+template <int NM, bool VEL>
 __global__ void __launch_bounds__(64) k_stokes_rays(const StokesParams p)
 {
     extern __shared__ double smem[];                  // the exponential's table, the Voigt function's (56 doubles), the patterns
@@ -78,8 +80,8 @@ __global__ void __launch_bounds__(64) k_stokes_rays(const StokesParams p)
     // the kept broadening arrays of the column (every column of a call has them: checked on the host)
     const double* aD_c = p.aDamp + col * (size_t)p.NlinesA * Ns;
     const double* vB_c = p.vBroad + col * (size_t)p.Natoms * Ns;
-    const double* vL_c = p.vlos + col * Ns;
     const double* fld = p.field + (size_t)blockIdx.y * Ns;
+    const double* vL_c = VEL ? fld + 3 * p.fstride : p.vlos + col * Ns;
     const double wav = p.wavelength[la], u_la = p.u_la[la];
     const W2Dev wf{etab};
 
@@ -113,7 +115,7 @@ __global__ void __launch_bounds__(64) k_stokes_rays(const StokesParams p)
             if (t.is_line) {
                 const double nd = t.a * (ni - t.g * nj);          // n_i Vij - n_j Vji = nd phi, :279-280, :613
                 const int nc = p.pat_line[2 * t.row];
-                if (nc > 0 || fa.raydep) {
+                if (VEL || nc > 0 || fa.raydep) {
                     // a polarised line: split profiles from the kept broadening arrays (vlos is zero where none was given); a
                     // ray-dependent unpolarised one: the same profile function without a splitting (one evaluation), into eta_I and eps_I alone
                     const lds_f64* tab = ptab + lsxst::kCompDoubles * p.pat_line[2 * t.row + 1];
@@ -174,9 +176,10 @@ __global__ void __launch_bounds__(64) k_stokes_rays(const StokesParams p)
 }
 
 template <int NM>
-void launch_chunk(const StokesParams& p, dim3 grid, size_t lds, hipStream_t st)
+void launch_chunk(const StokesParams& p, bool vel, dim3 grid, size_t lds, hipStream_t st)
 {
-    hipLaunchKernelGGL((k_stokes_rays<NM>), grid, dim3(64), lds, st, p);
+    if (vel) hipLaunchKernelGGL((k_stokes_rays<NM, true>), grid, dim3(64), lds, st, p);
+    else hipLaunchKernelGGL((k_stokes_rays<NM, false>), grid, dim3(64), lds, st, p);
 }
 
 } // namespace
@@ -202,6 +205,7 @@ int lsxd::stokes_check_state(const lsx_ctx* c, const char* who, const StokesCall
     int rc;
     std::string msg;
     if ((rc = lsxst::check_field((size_t)s.ncol * c->Nspace, s.B, s.gammaB, s.chiB, msg))) return fail(rc, "%s: %s", who, msg.c_str());
+    if (s.vlos && (rc = lsxst::check_velocity((size_t)s.ncol * c->Nspace, s.vlos, msg))) return fail(rc, "%s: %s", who, msg.c_str());
     if ((rc = lsxst::check_patterns(c->Nlines, s.ncomp, s.alpha, s.strength, s.shift, msg))) return fail(rc, "%s: %s", who, msg.c_str());
     if ((rc = final_check_depths(c, who))) return rc;
     if ((rc = final_check_columns(c, who, s.col0, s.ncol, FINAL_OTHER_ANGLE))) return rc;
@@ -231,8 +235,8 @@ int lsxd::stokes_patterns(const lsx_ctx* c, const char* who, const StokesCall& s
 int lsxd::stokes_upload_field(lsx_ctx* c, const StokesCall& s, size_t b0, size_t nb, double* d_field)
 {
     const size_t Ns = (size_t)c->Nspace;
-    const double* const src[3] = {s.B, s.gammaB, s.chiB};
-    for (int a = 0; a < 3; ++a)
+    const double* const src[4] = {s.B, s.gammaB, s.chiB, s.vlos};
+    for (int a = 0; a < s.nfield(); ++a)
         HIPCHK(hipMemcpyAsync(d_field + (size_t)a * nb * Ns, src[a] + b0 * Ns, nb * Ns * 8, hipMemcpyHostToDevice, c->stream));
     return LSX_OK;
 }
@@ -268,12 +272,13 @@ int lsxd::stokes_rays_run(lsx_ctx* c, const char* who, const StokesCall& s, doub
     // columns per pass: the field and the result of a pass stay under the cap (one column's need if that alone is more)
     GrowBuf& work = c->buf[BUF_STOKES_WORK];
     const size_t head = ((size_t)nmu + 1) & ~(size_t)1;
-    const size_t wcol = per + 3 * (size_t)Ns;
+    const size_t nf = (size_t)s.nfield();
+    const size_t wcol = per + nf * (size_t)Ns;
     const size_t chunk = pass_columns(ncol, work.cap, kWorkCapDefault, wcol, kGridYLimit);
     if ((rc = work.reserve(c, (head + chunk * wcol) * 8))) return rc;
     double* d_mu = work.as<double>();
     double* d_field = d_mu + head;
-    double* d_out = d_field + chunk * 3 * (size_t)Ns;
+    double* d_out = d_field + chunk * nf * (size_t)Ns;
     HIPCHK(hipMemcpyAsync(d_mu, s.mu, (size_t)nmu * 8, hipMemcpyHostToDevice, c->stream));
 
     StokesParams p{};
@@ -299,7 +304,7 @@ int lsxd::stokes_rays_run(lsx_ctx* c, const char* who, const StokesCall& s, doub
         // tables) is redone per launch.  That the former outweighs the latter is supposed, not measured
         for (int m0 = 0; m0 < nmu; ++m0) {
             p.mu0 = m0;
-            launch_chunk<1>(p, grid, lds, c->stream);
+            launch_chunk<1>(p, s.vlos != nullptr, grid, lds, c->stream);
         }
         HIPCHK(hipGetLastError());
         if (sink) {
@@ -319,4 +324,14 @@ extern "C" int lsx_hip_stokes_rays(lsx_ctx* c, int32_t nmu, const double* mu, in
 {
     const StokesCall s{nmu, mu, col0, ncol, la0, nla, B, gammaB, chiB, ncomp, alpha, strength, shift};
     return stokes_rays_run(c, "lsx_hip_stokes_rays", s, out, nbytes, nullptr);
+}
+
+extern "C" int lsx_hip_velocity_stokes_rays(lsx_ctx* c, int32_t nmu, const double* mu, int32_t col0, int32_t ncol, int32_t la0, int32_t nla,
+                                            const double* B, const double* gammaB, const double* chiB,
+                                            const int32_t* ncomp, const int32_t* alpha, const double* strength, const double* shift,
+                                            double* out, size_t nbytes, const double* vlos)
+{
+    if (!vlos) return lsx_hip_stokes_rays(c, nmu, mu, col0, ncol, la0, nla, B, gammaB, chiB, ncomp, alpha, strength, shift, out, nbytes);
+    const StokesCall s{nmu, mu, col0, ncol, la0, nla, B, gammaB, chiB, ncomp, alpha, strength, shift, vlos};
+    return stokes_rays_run(c, "lsx_hip_velocity_stokes_rays", s, out, nbytes, nullptr);
 }

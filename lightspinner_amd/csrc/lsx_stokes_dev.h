@@ -253,12 +253,24 @@ LSXST_HD void delo_step(Ray& r, const Acc& a, double adz_zmu, const W2F& wf, boo
 constexpr int kNodeDoubles = 11;
 constexpr int kStateDoubles = 5;       // the ray's I, Q, U, V and dt after the step into a depth
 
+// (With a velocity in the call there are up to nine variants: the fourth parameter is vlos.)
 // the field of a variant: par 0 B, 1 gammaB, 2 chiB; up: +a/2, else -a/2 (p + a/2 and p - a/2 as a caller forms them)
 LSXST_HD void field_variant(int par, bool up, double amp, double& B, double& g, double& x)
 {
     const double h = 0.5 * amp;
     double& t = par == 0 ? B : (par == 1 ? g : x);
     t = up ? t + h : t - h;
+}
+// ... in a call with a velocity (include/lsx_hip_stokes_velocity.h): par 3 moves the depth's line-of-sight velocity vl and leaves the
+// field, and so the geometry, alone; par 0, 1, 2 are the function above (its text, so that those variants keep their bits)
+LSXST_HD void field_variant(int par, bool up, double amp, double& B, double& g, double& x, double& vl)
+{
+    if (par == 3) {
+        const double h = 0.5 * amp;
+        vl = up ? vl + h : vl - h;
+    } else {
+        field_variant(par, up, amp, B, g, x);
+    }
 }
 
 // node <-> 11 doubles `stride` apart (the wavelength runs fastest in the stores: stride = the window's length)

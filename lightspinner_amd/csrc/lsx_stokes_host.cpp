@@ -94,7 +94,7 @@ void walk(int Ns, const double* z, double mu, bool thermal, double Be, double Bn
 }
 
 // the lines handed over to lsx_stokes_host_window / lsx_stokes_host_response and what a point of a ray makes of them: eta, rho, eps
-// of wavelength q at depth k with the field (Bk, gk, xk) there
+// of wavelength q at depth k with the field (Bk, gk, xk) and the line-of-sight velocity vl there
 struct WindowLines {
     int Ns, nla, nlines;
     const double *wav, *chi_c, *eta_c, *lambda0, *nd, *ne, *aD, *vB, *vlos;
@@ -102,7 +102,7 @@ struct WindowLines {
     const int32_t* line;
     const double *tab, *W;
 
-    Acc at(int q, int k, double Bk, double gk, double xk, double mu) const
+    Acc at(int q, int k, double Bk, double gk, double xk, double vl, double mu) const
     {
         const double w = wav[q];
         Acc a;
@@ -116,7 +116,7 @@ struct WindowLines {
             const double v = (w - l0) * kCLight / (vb * l0);
             const double rn = 1.0 / (std::sqrt(M_PI) * vb);
             const double vZ = nc > 0 ? kLarmor * (kNM_TO_M * l0) * Bk / vb : 0.0;
-            const Prof pr = line_profiles(nc, tab + kCompDoubles * line[2 * l + 1], aD[x], v + 1.0 * (mu * vlos[k] / vb), vZ, W);
+            const Prof pr = line_profiles(nc, tab + kCompDoubles * line[2 * l + 1], aD[x], v + 1.0 * (mu * vl / vb), vZ, W);
             if (nc > 0) line_add(a, nd[x], ne[x], pr, rn, g);
             else line_add_plain(a, nd[x], ne[x], pr, rn);
         }
@@ -228,7 +228,7 @@ int lsx_stokes_host_window(int32_t Ns, int32_t nla, const double* z, const doubl
     const WindowLines wl{Ns, nla, nlines, wav, chi_c, eta_c, lambda0, nd, ne, aD, vB, vlos, active, line.data(), tab.data(), voigt_table()};
     for (int q = 0; q < nla; ++q) {
         const double w = wav[q];
-        auto acc_at = [&](int k) { return wl.at(q, k, B[k], gammaB[k], chiB[k], mu); };
+        auto acc_at = [&](int k) { return wl.at(q, k, B[k], gammaB[k], chiB[k], vlos[k], mu); };
         double o[4];
         walk(Ns, z, mu, !lower_zero, planck(temperature[Ns - 1], w), planck(temperature[Ns - 2], w), ulp, endpoint != 0, acc_at, o);
         for (int s = 0; s < 4; ++s) out[(size_t)s * nla + q] = o[s];
@@ -236,32 +236,34 @@ int lsx_stokes_host_window(int32_t Ns, int32_t nla, const double* z, const doubl
     return LSX_OK;
 }
 
-// What lsx_hip_response_stokes computes for one column, one angle and a window (include/lsx_hip_stokes_response.h), by its two
-// stages through the same header functions: the nodes of every depth under every field variant (node_store), then response_walk.
-// Arguments as lsx_stokes_host_window (the end point as the kernel has it), then params, amplitude[3], nk, ks (null: all depths).
-// -> rf [npar][4][nla][nk], stokes [4][nla] (may be null).  Returns the code of the entry's rules for field, patterns and these.
-int lsx_stokes_host_response(int32_t Ns, int32_t nla, const double* z, const double* temperature, const double* wav, const double* chi_c,
-                             const double* eta_c, int32_t nlines, const double* lambda0, const double* nd, const double* ne,
-                             const double* aD, const double* vB, const uint8_t* active, const int32_t* ncomp, const int32_t* alpha,
-                             const double* strength, const double* shift, const double* vlos, const double* B, const double* gammaB,
-                             const double* chiB, double mu, int32_t lower_zero, int32_t ulp, uint32_t params, const double* amplitude,
-                             int32_t nk, const int32_t* ks, double* rf, double* stokes)
+} // extern "C"
+
+namespace {
+
+// lsx_stokes_host_response (nmax 3) and lsx_stokes_host_response_v (nmax 4: bit 8, vlos, and amplitude[4]) below
+int response_host(int nmax, int32_t Ns, int32_t nla, const double* z, const double* temperature, const double* wav, const double* chi_c,
+                  const double* eta_c, int32_t nlines, const double* lambda0, const double* nd, const double* ne,
+                  const double* aD, const double* vB, const uint8_t* active, const int32_t* ncomp, const int32_t* alpha,
+                  const double* strength, const double* shift, const double* vlos, const double* B, const double* gammaB,
+                  const double* chiB, double mu, int32_t lower_zero, int32_t ulp, uint32_t params, const double* amplitude,
+                  int32_t nk, const int32_t* ks, double* rf, double* stokes)
 {
-    if (Ns < 3 || nla < 1 || !(mu > 0.0 && mu <= 1.0) || !rf) return LSX_EINVAL;
+    if (Ns < 3 || nla < 1 || !(mu > 0.0 && mu <= 1.0) || !rf || !vlos) return LSX_EINVAL;
     std::string msg;
     int rc = check_field((size_t)Ns, B, gammaB, chiB, msg);
+    if (!rc && nmax > 3) rc = check_velocity((size_t)Ns, vlos, msg);
     if (!rc) rc = check_patterns(nlines, ncomp, alpha, strength, shift, msg);
-    if (!rc) rc = check_response(params, amplitude, Ns, nk, ks, 1, 0, B, msg);
+    if (!rc) rc = check_response(params, amplitude, Ns, nk, ks, 1, 0, B, msg, nmax);
     if (rc) return rc;
     std::vector<uint8_t> wanted((size_t)(nlines > 0 ? nlines : 1), 1);
     std::vector<int32_t> line;
     std::vector<double> tab;
     if ((rc = pack_patterns(nlines, ncomp, alpha, strength, shift, wanted, line, tab, msg))) return rc;
     tab.resize(tab.size() + kCompDoubles, 0.0);
-    int par[3] = {0, 0, 0};
+    int par[kMaxResponseParams] = {0, 0, 0, 0};
     const int npar = response_params(params, par);
     const int nvar = 1 + 2 * npar, nkk = ks ? nk : Ns;
-    double amp[3] = {0.0, 0.0, 0.0};
+    double amp[kMaxResponseParams] = {0.0, 0.0, 0.0, 0.0};
     for (int i = 0; i < npar; ++i) amp[i] = amplitude[par[i]];
     std::vector<uint8_t> kreq((size_t)Ns, ks ? 0 : 1);
     for (int i = 0; i < nkk && ks; ++i) kreq[ks[i]] = 1;
@@ -272,10 +274,10 @@ int lsx_stokes_host_response(int32_t Ns, int32_t nla, const double* z, const dou
     for (int k = 0; k < Ns; ++k)
         for (int var = 0; var < nvar; ++var) {
             if (var > 0 && !kreq[k]) continue;
-            double Bk = B[k], gk = gammaB[k], xk = chiB[k];
-            if (var > 0) field_variant(par[(var - 1) >> 1], ((var - 1) & 1) == 0, amp[(var - 1) >> 1], Bk, gk, xk);
+            double Bk = B[k], gk = gammaB[k], xk = chiB[k], vlk = vlos[k];
+            if (var > 0) field_variant(par[(var - 1) >> 1], ((var - 1) & 1) == 0, amp[(var - 1) >> 1], Bk, gk, xk, vlk);
             for (int q = 0; q < nla; ++q)
-                node_store(wl.at(q, k, Bk, gk, xk, mu), nodes.data() + ((size_t)var * Ns + k) * kNodeDoubles * S + q, S);
+                node_store(wl.at(q, k, Bk, gk, xk, vlk, mu), nodes.data() + ((size_t)var * Ns + k) * kNodeDoubles * S + q, S);
         }
     // ---- stage 2 ----
     const W2Host wf{ulp};
@@ -306,6 +308,39 @@ int lsx_stokes_host_response(int32_t Ns, int32_t nla, const double* z, const dou
         for (int c = 0; c < 4 && stokes; ++c) stokes[(size_t)c * nla + q] = Sv[c];
     }
     return LSX_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+// What lsx_hip_response_stokes computes for one column, one angle and a window (include/lsx_hip_stokes_response.h), by its two
+// stages through the same header functions: the nodes of every depth under every field variant (node_store), then response_walk.
+// Arguments as lsx_stokes_host_window (the end point as the kernel has it), then params, amplitude[3], nk, ks (null: all depths).
+// -> rf [npar][4][nla][nk], stokes [4][nla] (may be null).  Returns the code of the entry's rules for field, patterns and these.
+int lsx_stokes_host_response(int32_t Ns, int32_t nla, const double* z, const double* temperature, const double* wav, const double* chi_c,
+                             const double* eta_c, int32_t nlines, const double* lambda0, const double* nd, const double* ne,
+                             const double* aD, const double* vB, const uint8_t* active, const int32_t* ncomp, const int32_t* alpha,
+                             const double* strength, const double* shift, const double* vlos, const double* B, const double* gammaB,
+                             const double* chiB, double mu, int32_t lower_zero, int32_t ulp, uint32_t params, const double* amplitude,
+                             int32_t nk, const int32_t* ks, double* rf, double* stokes)
+{
+    return response_host(3, Ns, nla, z, temperature, wav, chi_c, eta_c, nlines, lambda0, nd, ne, aD, vB, active, ncomp, alpha, strength, shift, vlos,
+                         B, gammaB, chiB, mu, lower_zero, ulp, params, amplitude, nk, ks, rf, stokes);
+}
+
+// What lsx_hip_velocity_response_stokes computes (include/lsx_hip_stokes_velocity.h): the same arguments, the velocity handed over IS
+// vlos here, with bit 8 of params (the response to vlos, the fourth of rf's parameters) and amplitude[4].  The rows of B, gammaB and
+// chiB are those of lsx_stokes_host_response bit for bit: one function, and the variants of the field leave the velocity alone.
+int lsx_stokes_host_response_v(int32_t Ns, int32_t nla, const double* z, const double* temperature, const double* wav, const double* chi_c,
+                               const double* eta_c, int32_t nlines, const double* lambda0, const double* nd, const double* ne,
+                               const double* aD, const double* vB, const uint8_t* active, const int32_t* ncomp, const int32_t* alpha,
+                               const double* strength, const double* shift, const double* vlos, const double* B, const double* gammaB,
+                               const double* chiB, double mu, int32_t lower_zero, int32_t ulp, uint32_t params, const double* amplitude,
+                               int32_t nk, const int32_t* ks, double* rf, double* stokes)
+{
+    return response_host(4, Ns, nla, z, temperature, wav, chi_c, eta_c, nlines, lambda0, nd, ne, aD, vB, active, ncomp, alpha, strength, shift, vlos,
+                         B, gammaB, chiB, mu, lower_zero, ulp, params, amplitude, nk, ks, rf, stokes);
 }
 
 } // extern "C"

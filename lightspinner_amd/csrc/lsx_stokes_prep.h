@@ -107,30 +107,47 @@ inline int pack_patterns(int nlines, const int32_t* ncomp, const int32_t* alpha,
     return LSX_OK;
 }
 
+// ---- the velocity of a call (include/lsx_hip_stokes_velocity.h) ----
+// vlos: [count].  -> LSX_OK or LSX_EINVAL with a message.  Any finite velocity is taken: there is no bound
+inline int check_velocity(size_t count, const double* vlos, std::string& msg)
+{
+    char buf[120];
+    for (size_t i = 0; i < count; ++i)
+        if (!std::isfinite(vlos[i])) {
+            snprintf(buf, sizeof buf, "vlos at point %zu is not finite (%g)", i, vlos[i]);
+            msg = buf;
+            return LSX_EINVAL;
+        }
+    return LSX_OK;
+}
+
 // ---- the rules lsx_hip_response_stokes adds (include/lsx_hip_stokes_response.h) ----
-// the requested parameters in the order B, gammaB, chiB -> par[npar] (0, 1, 2); returns npar
-inline int response_params(uint32_t params, int par[3])
+constexpr int kMaxResponseParams = 4;      // B, gammaB, chiB and, in a call with a velocity, vlos
+// the requested parameters in the order B, gammaB, chiB, vlos -> par[npar] (0, 1, 2, 3); returns npar
+inline int response_params(uint32_t params, int par[kMaxResponseParams])
 {
     int n = 0;
-    for (int b = 0; b < 3; ++b)
+    for (int b = 0; b < kMaxResponseParams; ++b)
         if (params & (1u << b)) par[n++] = b;
     return n;
 }
 
-// params, amplitude[3], the depths (ks null: all Ns, nk is not looked at) and, where B is requested, B >= a_B / 2 at every requested
-// depth of the ncol columns of B [ncol][Ns] (col0: the first one's number, for the message).  -> LSX_OK or LSX_EINVAL with a message
+// params, amplitude[nmax], the depths (ks null: all Ns, nk is not looked at) and, where B is requested, B >= a_B / 2 at every requested
+// depth of the ncol columns of B [ncol][Ns] (col0: the first one's number, for the message).  nmax: 3, or 4 in a call with a velocity
+// (bit 8, vlos, is known only there; vlos has no rule like B's).  -> LSX_OK or LSX_EINVAL with a message
 inline int check_response(uint32_t params, const double* amplitude, int Ns, int32_t nk, const int32_t* ks, size_t ncol, int col0,
-                          const double* B, std::string& msg)
+                          const double* B, std::string& msg, int nmax = 3)
 {
-    static const char* const name[3] = {"B", "gammaB", "chiB"};
+    static const char* const name[kMaxResponseParams] = {"B", "gammaB", "chiB", "vlos"};
     char buf[200];
-    if (params == 0 || (params & ~7u)) {
-        snprintf(buf, sizeof buf, "params = 0x%x: need at least one of the bits B (1), gammaB (2), chiB (4) and no other", (unsigned)params);
+    if (params == 0 || (params & ~((1u << nmax) - 1u))) {
+        snprintf(buf, sizeof buf, "params = 0x%x: need at least one of the bits B (1), gammaB (2), chiB (4)%s and no other", (unsigned)params,
+                 nmax > 3 ? ", vlos (8)" : "");
         msg = buf;
         return LSX_EINVAL;
     }
     if (!amplitude) { msg = "null amplitude"; return LSX_EINVAL; }
-    for (int b = 0; b < 3; ++b)
+    for (int b = 0; b < nmax; ++b)
         if ((params & (1u << b)) && !(std::isfinite(amplitude[b]) && amplitude[b] > 0.0)) {
             snprintf(buf, sizeof buf, "the amplitude of %s is %g: it must be finite and positive", name[b], amplitude[b]);
             msg = buf;

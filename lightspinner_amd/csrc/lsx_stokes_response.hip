@@ -17,6 +17,10 @@
 //   k_response_walk    lane = wavelength, block z = angle; no profile function.  response_walk (lsx_stokes_dev.h): the walk up over
 //                      the stored nodes keeps the ray's state at every depth; the walk down carries the 4 x 4 matrix T_m and redoes,
 //                      per requested depth, parameter and sign, the steps that depth's node enters.
+// With a velocity in the call (include/lsx_hip_stokes_velocity.h) vlos is a fourth parameter of exactly this
+// structure: its variants move the velocity of one depth, leave the geometry and re-form the profiles, so there are up to nine blocks
+// a depth; k_response_nodes<true> reads the call's velocity in the context's place and forms every line of the window itself.  The
+// walk sees only more variants.
 // The work arrays are padded to whole wavefronts of wavelengths, so that a spare lane (it walks the window's last wavelength: the
 // exponential's table is read wave-wide) has a slot of its own: one writer per value.
 #include <hip/hip_runtime.h>
@@ -29,6 +33,7 @@
 #include "lsx_final_host.h"
 #include "lsx_stokes_dev.h"
 #include "lsx_stokes_prep.h"
+#include "lsx_stokes_response_nodes.h"
 
 using namespace lsxd;
 
@@ -36,110 +41,10 @@ namespace {
 
 constexpr size_t kWorkCapDefault = (size_t)256 << 20;      // bytes (include/lsx_hip_stokes_response.h)
 
-struct RespParams {
-    // ---- what k_stokes_rays reads (lsx_stokes.hip, StokesParams) ----
-    int32_t Ns, Nspect, NLtot, Natoms, NlinesA, Ncont, L, Nrays;
-    int32_t col0, nmu, mu0;     // first column of the launch; angles of the call; the angle of this launch of k_response_nodes
-    int32_t la0, nla;
-    int32_t phi_compact, sca_per_lambda, phi_G;
-    int32_t ntab;
-    int64_t til_col, phi_col, sca_col, fstride;
-    const double *wavelength, *u_la, *exp2_tab, *voigt_W, *mu;
-    const int32_t* la_ptr;
-    const FinalEnt* ents;
-    const int32_t* la_tile;
-    const double *height, *temperature, *n, *nsr, *bgchi_T, *bgeta_T, *J_T, *E_T, *sca, *phi_T;
-    const double *aDamp, *vBroad, *vlos;
-    const uint8_t* prof_kind;
-    const int32_t* bnd;
-    const int32_t* pat_line;
-    const double* pat_tab;
-    const double* field;
-    // ---- the response's own ----
-    int32_t npar, nvar, nk, nlaP;       // requested parameters, 1 + 2 npar, requested depths, nla rounded up to whole wavefronts
-    const int32_t* par;                 // [npar] the requested parameters (0 B, 1 gammaB, 2 chiB)
-    const double* amp;                  // [npar] their amplitudes
-    const int32_t* ks;                  // [nk] requested depths, or null: all
-    const int32_t* kreq;                // [Ns]: 1 where the depth is requested
-    double* nodes;                      // [launch column][nmu][nvar][Ns][11][nlaP]
-    double* state;                      // [launch column][nmu][Ns][5][nlaP]
-    double* rf;                         // [launch column][npar][4][nla][nk][nmu]
-};
-
 struct W2Dev {                  // the linear rule's weights as the other final passes form them (lsx_dev.h)
     const lds_f64* etab;
     __device__ __forceinline__ void operator()(double dtau, double& w0, double& w1) const { w2(dtau, w0, w1, etab); }
 };
-
-__device__ __forceinline__ size_t node_offset(const RespParams& p, size_t cl, int m, int var, int k)
-{
-    return ((((cl * p.nmu + m) * p.nvar + var) * p.Ns + k) * (size_t)lsxst::kNodeDoubles) * p.nlaP;
-}
-
-// ---- stage 1: the node of one depth under one variant of the field ----
-__global__ void __launch_bounds__(64) k_response_nodes(const RespParams p)
-{
-    const int Ns = p.Ns, L = p.L;
-    const int k = blockIdx.z / p.nvar, var = blockIdx.z - k * p.nvar;
-    if (var > 0 && !p.kreq[k]) return;                    // (block-uniform) a variant is read at requested depths only
-    extern __shared__ double smem[];                      // the Voigt function's table (56 doubles), the patterns
-    if (threadIdx.x < 56) smem[threadIdx.x] = p.voigt_W ? p.voigt_W[threadIdx.x] : 0.0;
-    for (int e = threadIdx.x; e < p.ntab; e += 64) smem[64 + e] = p.pat_tab[e];
-    __syncthreads();
-    const lds_f64* vtab = (const lds_f64*)smem;
-    const lds_f64* ptab = vtab + 64;
-
-    const int q_raw = blockIdx.x * 64 + threadIdx.x;
-    const int q = q_raw < p.nla ? q_raw : p.nla - 1;
-    const int la = p.la0 + q;
-    const size_t col = (size_t)p.col0 + blockIdx.y;
-    const FinalColumn f = final_column(p, col, la);
-    const FinalAngles fa = final_angles(p, col);
-    const double* aD_c = p.aDamp + col * (size_t)p.NlinesA * Ns;
-    const double* vB_c = p.vBroad + col * (size_t)p.Natoms * Ns;
-    const double* vL_c = p.vlos + col * Ns;
-    const double* fld = p.field + (size_t)blockIdx.y * Ns;
-    const double wav = p.wavelength[la], u_la = p.u_la[la];
-    const double mu = p.mu[p.mu0];
-
-    const double Ev = f.Eb ? f.Eb[(size_t)k * L] : 0.0;
-    const double c0 = f.bgchi[(size_t)k * L];
-    const double h0 = f.bgeta[(size_t)k * L] + f.sca[(size_t)k * f.sstr] * f.Jd[(size_t)k * L];
-    double Bk = fld[k], gk = fld[p.fstride + k], xk = fld[2 * p.fstride + k];
-    if (var > 0) lsxst::field_variant(p.par[(var - 1) >> 1], ((var - 1) & 1) == 0, p.amp[(var - 1) >> 1], Bk, gk, xk);
-    lsxst::Acc acc;
-    lsxst::acc_init(acc, c0, h0);
-    const lsxst::Geo geo = lsxst::geometry(gk, xk, mu);
-    for (int e = f.e0; e < f.e1; ++e) {
-        const FinalEnt& t = p.ents[e];
-        const double ni = f.n_col[(size_t)t.li * Ns + k], nj = f.n_col[(size_t)t.lj * Ns + k];
-        if (t.is_line) {
-            const double nd = t.a * (ni - t.g * nj);
-            const int nc = p.pat_line[2 * t.row];
-            if (nc > 0 || fa.raydep) {
-                const lds_f64* tab = ptab + lsxst::kCompDoubles * p.pat_line[2 * t.row + 1];
-                const double vb = vB_c[(size_t)t.atom * Ns + k], ad = aD_c[(size_t)t.row * Ns + k], vl = vL_c[k];
-                const double v = (wav - t.lambda0) * kCLight / (vb * t.lambda0);
-                const double rn = 1.0 / (sqrt(M_PI) * vb);
-                const double vZ = nc > 0 ? lsxst::kLarmor * (kNM_TO_M * t.lambda0) * Bk / vb : 0.0;
-                const double ne = nj * t.Uc;
-                const lsxst::Prof pr = lsxst::line_profiles(nc, tab, ad, v + 1.0 * (mu * vl / vb), vZ, vtab);
-                if (nc > 0) lsxst::line_add(acc, nd, ne, pr, rn, geo);
-                else lsxst::line_add_plain(acc, nd, ne, pr, rn);
-            } else {
-                const size_t x = p.phi_compact ? (size_t)k : ((size_t)Ns + k) * p.Nrays;
-                const double pv = p.phi_T[phi_elem(col, p.phi_G, (size_t)p.phi_col, (size_t)t.phi_base, x, t.phi_len, t.phi_l)];
-                const double c1 = nd * pv, h1 = nj * (t.Uc * pv);
-                acc.eI += c1; acc.mI += h1;
-            }
-        } else {
-            const double pv = (f.nsr_col[(size_t)t.row * Ns + k] * Ev) * t.a;
-            const double c1 = ni * t.a - nj * pv, h1 = nj * (u_la * pv);
-            acc.eI += c1; acc.mI += h1;
-        }
-    }
-    lsxst::node_store(acc, p.nodes + node_offset(p, blockIdx.y, p.mu0, var, k) + q_raw, (size_t)p.nlaP);
-}
 
 // ---- stage 2: the walks of one ray ----
 struct ZDev {
@@ -213,7 +118,7 @@ extern "C" int lsx_hip_response_stokes_work_cap(lsx_ctx* c, size_t nbytes)
 
 // The argument rules of lsx_hip_response_stokes but the byte counts; nothing is launched.  (lsx_fit.hip asks them of its expanded
 // field before its first launch.)
-int lsxd::response_stokes_check(lsx_ctx* c, const char* who, const StokesCall& s, uint32_t params, const double amplitude[3], int32_t nk,
+int lsxd::response_stokes_check(lsx_ctx* c, const char* who, const StokesCall& s, uint32_t params, const double* amplitude, int32_t nk,
                                 const int32_t* ks)
 {
     // ---- first what lsx_hip_stokes_rays checks, in its order ----
@@ -223,8 +128,9 @@ int lsxd::response_stokes_check(lsx_ctx* c, const char* who, const StokesCall& s
     // ---- ... then the response's own rules ----
     const int Ns = c->Nspace;
     std::string msg;
-    if ((rc = lsxst::check_response(params, amplitude, Ns, nk, ks, (size_t)s.ncol, s.col0, s.B, msg))) return fail(rc, "%s: %s", who, msg.c_str());
-    int par[3] = {0, 0, 0};
+    if ((rc = lsxst::check_response(params, amplitude, Ns, nk, ks, (size_t)s.ncol, s.col0, s.B, msg, s.nfield())))
+        return fail(rc, "%s: %s", who, msg.c_str());
+    int par[lsxst::kMaxResponseParams] = {0, 0, 0, 0};
     const int nvar = 1 + 2 * lsxst::response_params(params, par);
     if ((int64_t)Ns * nvar > 65535 || s.nmu > 65535)
         return fail(LSX_EUNSUPPORTED, "%s: Nspace x (1 + 2 parameters) = %lld or nmu = %d is above a grid's 65535", who,
@@ -235,7 +141,7 @@ int lsxd::response_stokes_check(lsx_ctx* c, const char* who, const StokesCall& s
 // The body of lsx_hip_response_stokes without its `stokes`.  sink null: the entry itself -- every pass is copied to rf.  An internal
 // caller (lsx_fit.hip) hands a sink instead and rf null: a pass's rf stays in the pass's device array and the sink is called in the
 // copy's place.  stokes_bytes: null, or the byte count of the entry's `stokes` to be checked with the others.
-int lsxd::response_stokes_run(lsx_ctx* c, const char* who, const StokesCall& s, uint32_t params, const double amplitude[3], int32_t nk,
+int lsxd::response_stokes_run(lsx_ctx* c, const char* who, const StokesCall& s, uint32_t params, const double* amplitude, int32_t nk,
                               const int32_t* ks, double* rf, size_t rf_bytes, const size_t* stokes_bytes, PassSink* sink)
 {
     // ---- everything is checked on the host before anything is launched ----
@@ -244,7 +150,7 @@ int lsxd::response_stokes_run(lsx_ctx* c, const char* who, const StokesCall& s, 
     if (rc) return rc;
     const int32_t nmu = s.nmu, ncol = s.ncol, nla = s.nla;
     const int Ns = c->Nspace;
-    int par[3] = {0, 0, 0};
+    int par[lsxst::kMaxResponseParams] = {0, 0, 0, 0};
     const int npar = lsxst::response_params(params, par);
     const int nvar = 1 + 2 * npar;
     const int nkk = ks ? nk : Ns;
@@ -258,10 +164,11 @@ int lsxd::response_stokes_run(lsx_ctx* c, const char* who, const StokesCall& s, 
     HIPCHK(hipSetDevice(c->device));
     if ((rc = final_tables(c, who))) return rc;
 
-    // the tables of the call: [pat_line | par | kreq | ks], [amp | pat_tab]
+    // the tables of the call: [pat_line | par | kreq | ks], [amp | pat_tab]; par and amp hold kMaxResponseParams entries, the first
+    // npar in use
     std::vector<int32_t> ints(pat_line);
     const size_t o_par = ints.size();
-    ints.insert(ints.end(), par, par + 3);
+    ints.insert(ints.end(), par, par + lsxst::kMaxResponseParams);
     const size_t o_kreq = ints.size();
     ints.resize(o_kreq + Ns, ks ? 0 : 1);
     const size_t o_ks = ints.size();
@@ -270,9 +177,10 @@ int lsxd::response_stokes_run(lsx_ctx* c, const char* who, const StokesCall& s, 
         ints.push_back(ks[i]);
     }
     const size_t int_bytes = (ints.size() * sizeof(int32_t) + 7) & ~(size_t)7;
-    const double amps[4] = {amplitude[par[0]], amplitude[par[npar > 1 ? 1 : 0]], amplitude[par[npar > 2 ? 2 : 0]], 0.0};
+    double amps[lsxst::kMaxResponseParams] = {0.0, 0.0, 0.0, 0.0};
+    for (int i = 0; i < npar; ++i) amps[i] = amplitude[par[i]];
     GrowBuf& tab = c->buf[BUF_STRESP_TAB];
-    if ((rc = tab.reserve(c, int_bytes + (4 + std::max<size_t>(1, pat_tab.size())) * 8))) return rc;
+    if ((rc = tab.reserve(c, int_bytes + (lsxst::kMaxResponseParams + std::max<size_t>(1, pat_tab.size())) * 8))) return rc;
     HIPCHK(hipMemcpyAsync(tab.p, ints.data(), ints.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(tab.p + int_bytes, amps, sizeof amps, hipMemcpyHostToDevice, c->stream));
     if (!pat_tab.empty())
@@ -284,12 +192,13 @@ int lsxd::response_stokes_run(lsx_ctx* c, const char* who, const StokesCall& s, 
     const size_t nblk = ((size_t)nla + 63) / 64, nlaP = nblk * 64;
     const size_t head = ((size_t)nmu + 1) & ~(size_t)1;
     const size_t w_nodes = (size_t)nmu * nvar * Ns * lsxst::kNodeDoubles * nlaP, w_state = (size_t)nmu * Ns * lsxst::kStateDoubles * nlaP;
-    const size_t wcol = w_nodes + w_state + per_rf + 3 * (size_t)Ns;
+    const size_t nf = (size_t)s.nfield();
+    const size_t wcol = w_nodes + w_state + per_rf + nf * (size_t)Ns;
     const size_t chunk = pass_columns(ncol, work.cap, kWorkCapDefault, wcol, kGridYLimit);
     if ((rc = work.reserve(c, (head + chunk * wcol) * 8))) return rc;
     double* d_mu = work.as<double>();
     double* d_field = d_mu + head;
-    double* d_nodes = d_field + chunk * 3 * (size_t)Ns;
+    double* d_nodes = d_field + chunk * nf * (size_t)Ns;
     double* d_state = d_nodes + chunk * w_nodes;
     double* d_rf = d_state + chunk * w_state;
     HIPCHK(hipMemcpyAsync(d_mu, s.mu, (size_t)nmu * 8, hipMemcpyHostToDevice, c->stream));
@@ -305,7 +214,7 @@ int lsxd::response_stokes_run(lsx_ctx* c, const char* who, const StokesCall& s, 
     p.ks = ks ? d_ints + o_ks : nullptr;
     p.par = d_ints + o_par;
     p.amp = (const double*)(tab.p + int_bytes);
-    p.pat_tab = p.amp + 4;
+    p.pat_tab = p.amp + lsxst::kMaxResponseParams;
     p.field = d_field;
     p.npar = npar; p.nvar = nvar; p.nk = nkk; p.nlaP = (int32_t)nlaP;
     p.nodes = d_nodes; p.state = d_state; p.rf = d_rf;
@@ -320,7 +229,9 @@ int lsxd::response_stokes_run(lsx_ctx* c, const char* who, const StokesCall& s, 
         // one launch of the nodes per angle (the profile function is evaluated per angle, as in lsx_stokes.hip), one of the walks for all
         for (int m0 = 0; m0 < nmu; ++m0) {
             p.mu0 = m0;
-            hipLaunchKernelGGL(k_response_nodes, dim3((unsigned)nblk, (unsigned)nb, (unsigned)(Ns * nvar)), dim3(64), lds_nodes, c->stream, p);
+            const dim3 grid((unsigned)nblk, (unsigned)nb, (unsigned)(Ns * nvar));
+            if (s.vlos) response_nodes_velocity(p, grid, lds_nodes, c->stream);
+            else hipLaunchKernelGGL(k_response_nodes<false>, grid, dim3(64), lds_nodes, c->stream, p);
         }
         p.mu0 = 0;
         hipLaunchKernelGGL(k_response_walk, dim3((unsigned)nblk, (unsigned)nb, (unsigned)nmu), dim3(64), lds_walk, c->stream, p);
@@ -351,5 +262,21 @@ extern "C" int lsx_hip_response_stokes(lsx_ctx* c, int32_t nmu, const double* mu
     // another kernel the device compiler contracts products and sums into fused operations differently: measured on an MI355X, a
     // quarter of the entries differ from k_stokes_rays' in the last bits (at most 1.2e-14 of I).  One more launch per angle
     if (stokes) return stokes_rays_run(c, "lsx_hip_stokes_rays", s, stokes, stokes_bytes, nullptr);
+    return LSX_OK;
+}
+
+extern "C" int lsx_hip_velocity_response_stokes(lsx_ctx* c, int32_t nmu, const double* mu, int32_t col0, int32_t ncol, int32_t la0, int32_t nla,
+                                                const double* B, const double* gammaB, const double* chiB,
+                                                const int32_t* ncomp, const int32_t* alpha, const double* strength, const double* shift,
+                                                uint32_t params, const double amplitude[4], int32_t nk, const int32_t* ks,
+                                                double* rf, size_t rf_bytes, double* stokes, size_t stokes_bytes, const double* vlos)
+{
+    const char* who = "lsx_hip_velocity_response_stokes";
+    if (!rf) return fail(LSX_EINVAL, "%s: null argument", who);
+    // (without a velocity: the rules and the kernels of lsx_hip_response_stokes, so bit 8 is refused as an unknown bit)
+    const StokesCall s{nmu, mu, col0, ncol, la0, nla, B, gammaB, chiB, ncomp, alpha, strength, shift, vlos};
+    const int rc = response_stokes_run(c, who, s, params, amplitude, nk, ks, rf, rf_bytes, stokes ? &stokes_bytes : nullptr, nullptr);
+    if (rc) return rc;
+    if (stokes) return stokes_rays_run(c, vlos ? "lsx_hip_velocity_stokes_rays" : "lsx_hip_stokes_rays", s, stokes, stokes_bytes, nullptr);
     return LSX_OK;
 }

@@ -7,6 +7,7 @@ import math
 import numpy as np
 
 PARAMETERS = ('B', 'gammaB', 'chiB')
+VELOCITY_PARAMETERS = PARAMETERS + ('vlos',)          # with the line-of-sight velocity as the fourth quantity (nnode of four counts)
 MAX_PARAMS = 24                       # LSX_FIT_MAX_PARAMS
 # status of a column of FieldFit
 CONVERGED, LAMBDA_CEILING, MAX_ITER = 0, 1, 2
@@ -34,9 +35,12 @@ def hat_basis(coordinate, node_positions):
     return out
 
 
-def stack_basis(B=None, gammaB=None, chiB=None):
-    """-> (basis [P][Nspace], nnode (3 ints)) from the parameters' own row sets (None: not fitted), in the library's order"""
+def stack_basis(B=None, gammaB=None, chiB=None, vlos=None):
+    """-> (basis [P][Nspace], nnode (3 ints)) from the parameters' own row sets (None: not fitted), in the library's order; with
+    `vlos` rows (the line-of-sight velocity is fitted too: include/lsx_hip_stokes_velocity.h) nnode has 4 ints"""
     rows = [None if b is None else np.atleast_2d(np.asarray(b, dtype=np.float64)) for b in (B, gammaB, chiB)]
+    if vlos is not None:
+        rows.append(np.atleast_2d(np.asarray(vlos, dtype=np.float64)))
     if all(r is None for r in rows):
         raise ValueError('stack_basis: no parameter is fitted')
     return np.concatenate([r for r in rows if r is not None], axis=0), tuple(0 if r is None else r.shape[0] for r in rows)
@@ -157,14 +161,14 @@ class Instrument:
 
 class FieldNormal:
     """What fit_field_normal returns: .chi2 [ncol], .grad [ncol][P], .hess [ncol][P][P], .field [ncol][3][Nspace] (the expanded
-    field: B, gammaB, chiB)."""
+    field: B, gammaB, chiB; with nnode of four counts [ncol][4][Nspace], the fourth row vlos)."""
 
     def __init__(self, chi2, grad, hess, field):
         self.chi2, self.grad, self.hess, self.field = chi2, grad, hess, field
 
 
 class FieldFit:
-    """What drivers.fit_field_columns returns: .nodes [ncol][P], .field [ncol][3][Nspace] (expanded from them), .chi2 [ncol],
+    """What drivers.fit_field_columns returns: .nodes [ncol][P], .field [ncol][3][Nspace] (expanded from them; [4] with vlos), .chi2 [ncol],
     .history [iterations + 1][ncol] (chi2 at the nodes held after each iteration; row 0 the start), .lam [ncol],
     .iterations [ncol] (those a column took part in), .status [ncol]: fit.CONVERGED, fit.LAMBDA_CEILING or fit.MAX_ITER, and
     .nnode.  Context.fit_field drops the column axis."""
@@ -174,7 +178,7 @@ class FieldFit:
         self.lam, self.iterations, self.status, self.nnode = lam, iterations, status, tuple(int(n) for n in nnode)
 
     def parameter(self, name):
-        """the nodes of 'B', 'gammaB' or 'chiB': [ncol][nnode]"""
-        i = PARAMETERS.index(name)
+        """the nodes of 'B', 'gammaB', 'chiB' or (fitted with four quantities) 'vlos': [ncol][nnode]"""
+        i = VELOCITY_PARAMETERS[:len(self.nnode)].index(name)
         o = sum(self.nnode[:i])
         return self.nodes[..., o:o + self.nnode[i]]

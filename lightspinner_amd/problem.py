@@ -268,6 +268,9 @@ class StokesResponse:
     Definitions: include/lsx_hip_stokes_response.h."""
     PARAMETERS = ('B', 'gammaB', 'chiB')
     DEFAULT_AMPLITUDES = {'B': 1e-3, 'gammaB': 1e-3, 'chiB': 1e-3}          # T, rad, rad
+    # with the velocity of the call (include/lsx_hip_stokes_velocity.h): 'vlos' is the fourth parameter, per m/s
+    VELOCITY_PARAMETERS = PARAMETERS + ('vlos',)
+    VELOCITY_DEFAULT_AMPLITUDES = dict(DEFAULT_AMPLITUDES, vlos=100.0)       # ..., m/s
 
     def __init__(self, rf, stokes, ks, mus, la0, amplitudes):
         self.rf, self.stokes, self.ks, self.mus, self.la0, self.amplitudes = rf, stokes, ks, mus, int(la0), amplitudes
@@ -662,14 +665,21 @@ class Engine:
                                                        int(np.prod(shape)) * 8, int(np.prod(shape[:2] + shape[3:])) * 8))
         return DepthRays(mu, la0, **out)
 
-    def stokes_rays(self, mus, B, gammaB, chiB, patterns=None, la0=0, nla=None, col0=0, ncol=None, work_cap_bytes=None):
+    def _velocity_lib(self, entry):
+        if not getattr(self.lib, 'has_stokes_velocity', False):
+            raise NotImplementedError('%s (%s) does not export %s: a line-of-sight velocity per call is taken by the HIP library '
+                                      'only' % (self.lib.path, self.lib.backend, entry))
+
+    def stokes_rays(self, mus, B, gammaB, chiB, patterns=None, la0=0, nla=None, col0=0, ncol=None, work_cap_bytes=None, vlos=None):
         """Emergent Stokes spectra in a magnetic field (Zeeman effect, field-free method: include/lsx_hip_stokes.h,
         lsx_hip_stokes_rays) of the up-going rays with direction cosines `mus`, for columns [col0, col0 + ncol) and the wavelengths
         [la0, la0 + nla) of the merged grid (nla None: to the end), from the current populations and J.  B [T], gammaB, chiB [rad]:
         [ncol][Nspace] (a single column may be 1-D, a scalar holds everywhere): strength, inclination against the vertical, azimuth.
         patterns: one entry per LINE of the problem in table order -- None (unpolarised), a zeeman.ZeemanComponents or an
         (alpha, strength, shift) triple; None: no line is polarised.  work_cap_bytes: the cap of the pass's device memory from this
-        call on (None: unchanged; 0: the default).  Read-only.  -> StokesRays.  Only the HIP library computes it."""
+        call on (None: unchanged; 0: the default).  vlos [m/s], shaped like B: the line-of-sight velocity of this call in the place of
+        the context's (include/lsx_hip_stokes_velocity.h, lsx_hip_velocity_stokes_rays; populations and J do not follow it); None: the
+        context's own.  Read-only.  -> StokesRays.  Only the HIP library computes it."""
         from . import zeeman
         if not getattr(self.lib, 'has_stokes', False):
             raise NotImplementedError('%s (%s) does not export lsx_hip_stokes_rays: polarised spectra are computed by the HIP '
@@ -684,19 +694,27 @@ class Engine:
         ncomp, alpha, strength, shift = zeeman.pack(patterns, self.problem.Nlines)
         out = np.empty((nc, 4, max(nla, 0), mu.shape[0]), dtype=np.float64)
         ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-        self.lib.check(self.lib.dll.lsx_hip_stokes_rays(self._h, mu.shape[0], _ptr(mu), int(col0), ncol, int(la0), nla, _ptr(fld[0]),
-                                                        _ptr(fld[1]), _ptr(fld[2]), ip(ncomp), ip(alpha), _ptr(strength), _ptr(shift),
-                                                        _ptr(out), out.nbytes))
+        args = (self._h, mu.shape[0], _ptr(mu), int(col0), ncol, int(la0), nla, _ptr(fld[0]), _ptr(fld[1]), _ptr(fld[2]), ip(ncomp),
+                ip(alpha), _ptr(strength), _ptr(shift), _ptr(out), out.nbytes)
+        if vlos is None:
+            self.lib.check(self.lib.dll.lsx_hip_stokes_rays(*args))
+        else:
+            self._velocity_lib('lsx_hip_velocity_stokes_rays')
+            vl = f64(np.broadcast_to(np.asarray(vlos, dtype=np.float64), (nc, Ns)))
+            self.lib.check(self.lib.dll.lsx_hip_velocity_stokes_rays(*args, _ptr(vl)))
         return StokesRays(mu, la0, out[:, 0], out[:, 1], out[:, 2], out[:, 3])
 
     def stokes_response(self, mus, B, gammaB, chiB, patterns=None, la0=0, nla=None, col0=0, ncol=None,
-                        parameters=StokesResponse.PARAMETERS, amplitudes=None, ks=None, work_cap_bytes=None):
+                        parameters=StokesResponse.PARAMETERS, amplitudes=None, ks=None, work_cap_bytes=None, vlos=None):
         """Response functions of the emergent Stokes vector to the field strength, inclination and azimuth at every depth
         (include/lsx_hip_stokes_response.h, lsx_hip_response_stokes): RF_p[k] = (S(p_k + a_p / 2) - S(p_k - a_p / 2)) / a_p, S what
         stokes_rays returns for the field changed at depth k of that column alone.  Arguments as stokes_rays, then
         parameters: some of 'B', 'gammaB', 'chiB'; amplitudes: a dict from those names to a_p (None, or a name left out: 1e-3 T,
         1e-3 rad); ks: the depths, strictly increasing (None: all).  B must be at least a_B / 2 at every requested depth where 'B'
-        is requested.  Read-only.  -> StokesResponse.  Only the HIP library computes it."""
+        is requested.  vlos [m/s], shaped like B: the velocity of this call as in stokes_rays; with it, or alone, 'vlos' may be among
+        the parameters (include/lsx_hip_stokes_velocity.h, lsx_hip_velocity_response_stokes; amplitude 100 m/s unless given) -- where
+        'vlos' is requested and no velocity is given, the velocity is zero.  Read-only.  -> StokesResponse.  Only the HIP library
+        computes it."""
         from . import zeeman
         if not getattr(self.lib, 'has_stokes_response', False):
             raise NotImplementedError('%s (%s) does not export lsx_hip_response_stokes: polarised spectra and their response '
@@ -704,14 +722,16 @@ class Engine:
         if work_cap_bytes is not None:
             self.lib.check(self.lib.dll.lsx_hip_response_stokes_work_cap(self._h, int(work_cap_bytes)))
         names = [parameters] if isinstance(parameters, str) else list(parameters)
+        vel = vlos is not None or 'vlos' in names
+        known = StokesResponse.VELOCITY_PARAMETERS if vel else StokesResponse.PARAMETERS
         for w in names:
-            if w not in StokesResponse.PARAMETERS:
-                raise ValueError("stokes_response: parameter %r is not one of 'B', 'gammaB', 'chiB'" % (w,))
-        names = [w for w in StokesResponse.PARAMETERS if w in names]
-        amps = dict(StokesResponse.DEFAULT_AMPLITUDES)
+            if w not in StokesResponse.VELOCITY_PARAMETERS:
+                raise ValueError("stokes_response: parameter %r is not one of 'B', 'gammaB', 'chiB', 'vlos'" % (w,))
+        names = [w for w in known if w in names]
+        amps = dict(StokesResponse.VELOCITY_DEFAULT_AMPLITUDES if vel else StokesResponse.DEFAULT_AMPLITUDES)
         amps.update(amplitudes or {})
-        amp = f64(np.array([amps[w] for w in StokesResponse.PARAMETERS], dtype=np.float64))
-        bits = sum(1 << StokesResponse.PARAMETERS.index(w) for w in names)
+        amp = f64(np.array([amps[w] for w in known], dtype=np.float64))
+        bits = sum(1 << known.index(w) for w in names)
         mu = f64(np.atleast_1d(np.asarray(mus, dtype=np.float64)).reshape(-1))
         ncol = self.ncol - int(col0) if ncol is None else int(ncol)
         nla = self.problem.Nspect - int(la0) if nla is None else int(nla)
@@ -723,10 +743,15 @@ class Engine:
         rf = np.empty((nc, len(names), 4, max(nla, 0), nk, mu.shape[0]), dtype=np.float64)
         out = np.empty((nc, 4, max(nla, 0), mu.shape[0]), dtype=np.float64)
         ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-        self.lib.check(self.lib.dll.lsx_hip_response_stokes(self._h, mu.shape[0], _ptr(mu), int(col0), ncol, int(la0), nla, _ptr(fld[0]),
-                                                            _ptr(fld[1]), _ptr(fld[2]), ip(ncomp), ip(alpha), _ptr(strength), _ptr(shift),
-                                                            bits, _ptr(amp), nk, None if kk is None else ip(kk), _ptr(rf), rf.nbytes,
-                                                            _ptr(out), out.nbytes))
+        args = (self._h, mu.shape[0], _ptr(mu), int(col0), ncol, int(la0), nla, _ptr(fld[0]), _ptr(fld[1]), _ptr(fld[2]), ip(ncomp),
+                ip(alpha), _ptr(strength), _ptr(shift), bits, _ptr(amp), nk, None if kk is None else ip(kk), _ptr(rf), rf.nbytes, _ptr(out),
+                out.nbytes)
+        if not vel:
+            self.lib.check(self.lib.dll.lsx_hip_response_stokes(*args))
+        else:
+            self._velocity_lib('lsx_hip_velocity_response_stokes')
+            vl = f64(np.broadcast_to(np.asarray(0.0 if vlos is None else vlos, dtype=np.float64), (nc, Ns)))
+            self.lib.check(self.lib.dll.lsx_hip_velocity_response_stokes(*args, _ptr(vl)))
         return StokesResponse({w: rf[:, i] for i, w in enumerate(names)}, StokesRays(mu, la0, out[:, 0], out[:, 1], out[:, 2], out[:, 3]),
                               np.arange(Ns, dtype=np.int32) if kk is None else kk, mu, la0, {w: float(amps[w]) for w in names})
 
@@ -769,8 +794,11 @@ class Engine:
         nla = self.problem.Nspect - int(la0) if nla is None else int(nla)
         nc, Ns = max(ncol, 0), self.problem.Nspace
         nn = np.ascontiguousarray(np.asarray(nnode).reshape(-1), dtype=np.int32)
-        if nn.shape[0] != 3:
-            raise ValueError('%s: nnode must hold three counts (B, gammaB, chiB)' % who)
+        if nn.shape[0] not in (3, 4):
+            raise ValueError('%s: nnode must hold three counts (B, gammaB, chiB) or four (then vlos)' % who)
+        nq = nn.shape[0]
+        if nq == 4:
+            self._velocity_lib('lsx_hip_velocity_%s' % who.replace('fit_field', 'fit'))
         P = max(int(nn.clip(min=0).sum()), 1)
         bas = f64(np.asarray(basis, dtype=np.float64).reshape(-1, Ns))
         if bas.shape[0] != int(nn.sum()):
@@ -779,13 +807,13 @@ class Engine:
         shape = (nc, 4, max(nla, 0) if instrument is None else instrument.nobs, mu.shape[0])
         ob = f64(np.asarray(obs, dtype=np.float64).reshape(shape))
         wt = None if weight is None else f64(np.broadcast_to(np.asarray(weight, dtype=np.float64), shape))
-        bs = None if base is None else f64(np.broadcast_to(np.asarray(base, dtype=np.float64), (nc, 3, Ns)))
+        bs = None if base is None else f64(np.broadcast_to(np.asarray(base, dtype=np.float64), (nc, nq, Ns)))
         ncomp, alpha, strength, shift = zeeman.pack(patterns, self.problem.Nlines)
         ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
         keep = (mu, nn, bas, x, ob, wt, bs, ncomp, alpha, strength, shift)
         head = [self._h, mu.shape[0], _ptr(mu), int(col0), ncol, int(la0), nla, ip(ncomp), ip(alpha), _ptr(strength), _ptr(shift), ip(nn),
                 _ptr(bas), None if bs is None else _ptr(bs), _ptr(x)]
-        return head, keep, _ptr(ob), None if wt is None else _ptr(wt), nc, P, Ns
+        return head, keep, _ptr(ob), None if wt is None else _ptr(wt), nc, P, Ns, nq
 
     def fit_field_normal(self, mus, basis, nnode, nodes, obs, weight=None, base=None, patterns=None, la0=0, nla=None, col0=0, ncol=None,
                          amplitudes=None, work_cap_bytes=None, instrument=None):
@@ -796,16 +824,24 @@ class Engine:
         stokes_rays; amplitudes as in stokes_response.  The response never leaves the device.  Read-only.
         instrument: a fit.Instrument over the window's nla wavelengths (include/lsx_hip_fit_instrument.h): obs and weight are
         [ncol][4][nobs][nmu], the Stokes vector and the Jacobian are smeared and sampled on the device before the sums; None: as ever.
+        nnode of FOUR counts (include/lsx_hip_stokes_velocity.h, lsx_hip_velocity_fit_normal): the line-of-sight velocity [m/s] is the
+        fourth quantity -- its rows last in basis, base [ncol][4][Nspace], .field [ncol][4][Nspace], amplitudes may name 'vlos'
+        (100 m/s).  The velocity is then base_3 + its nodes' expansion, never the context's own.
         -> fit.FieldNormal (.chi2, .grad, .hess, .field).  Only the HIP library computes it."""
         from .fit import FieldNormal
-        head, keep, ob, wt, nc, P, Ns = self._fit_args('fit_field_normal', mus, basis, nnode, nodes, obs, weight, base, patterns, la0, nla,
+        head, keep, ob, wt, nc, P, Ns, nq = self._fit_args('fit_field_normal', mus, basis, nnode, nodes, obs, weight, base, patterns, la0, nla,
                                                        col0, ncol, work_cap_bytes, instrument)
-        amps = dict(StokesResponse.DEFAULT_AMPLITUDES)
+        amps = dict(StokesResponse.VELOCITY_DEFAULT_AMPLITUDES if nq == 4 else StokesResponse.DEFAULT_AMPLITUDES)
         amps.update(amplitudes or {})
-        amp = f64(np.array([amps[w] for w in StokesResponse.PARAMETERS], dtype=np.float64))
+        amp = f64(np.array([amps[w] for w in StokesResponse.VELOCITY_PARAMETERS[:nq]], dtype=np.float64))
         chi2, grad, hess = np.empty(nc), np.empty((nc, P)), np.empty((nc, P, P))
-        field = np.empty((nc, 3, Ns))
-        if instrument is None:
+        field = np.empty((nc, nq, Ns))
+        if nq == 4:
+            st, keep_i = (None, None) if instrument is None else self._instrument('fit_field_normal', instrument, head[6])
+            self.lib.check(self.lib.dll.lsx_hip_velocity_fit_normal(*head, _ptr(amp), ob, wt, _ptr(chi2), _ptr(grad), _ptr(hess), _ptr(field),
+                                                                    None if st is None else C.byref(st)))
+            del keep_i
+        elif instrument is None:
             self.lib.check(self.lib.dll.lsx_hip_fit_field_normal(*head, _ptr(amp), ob, wt, _ptr(chi2), _ptr(grad), _ptr(hess), _ptr(field)))
         else:
             st, keep_i = self._instrument('fit_field_normal', instrument, head[6])
@@ -818,11 +854,15 @@ class Engine:
     def fit_field_chi2(self, mus, basis, nnode, nodes, obs, weight=None, base=None, patterns=None, la0=0, nla=None, col0=0, ncol=None,
                        work_cap_bytes=None, instrument=None):
         """chi2 of the field expanded from `nodes` (lsx_hip_fit_field_chi2): one Stokes pass and the reduction of fit_field_normal --
-        its chi2, bit for bit.  Arguments as fit_field_normal.  -> (chi2 [ncol], field [ncol][3][Nspace])."""
-        head, keep, ob, wt, nc, P, Ns = self._fit_args('fit_field_chi2', mus, basis, nnode, nodes, obs, weight, base, patterns, la0, nla,
-                                                       col0, ncol, work_cap_bytes, instrument)
-        chi2, field = np.empty(nc), np.empty((nc, 3, Ns))
-        if instrument is None:
+        its chi2, bit for bit.  Arguments as fit_field_normal.  -> (chi2 [ncol], field [ncol][3][Nspace], or [4] with nnode of four)."""
+        head, keep, ob, wt, nc, P, Ns, nq = self._fit_args('fit_field_chi2', mus, basis, nnode, nodes, obs, weight, base, patterns, la0, nla,
+                                                           col0, ncol, work_cap_bytes, instrument)
+        chi2, field = np.empty(nc), np.empty((nc, nq, Ns))
+        if nq == 4:
+            st, keep_i = (None, None) if instrument is None else self._instrument('fit_field_chi2', instrument, head[6])
+            self.lib.check(self.lib.dll.lsx_hip_velocity_fit_chi2(*head, ob, wt, _ptr(chi2), _ptr(field), None if st is None else C.byref(st)))
+            del keep_i
+        elif instrument is None:
             self.lib.check(self.lib.dll.lsx_hip_fit_field_chi2(*head, ob, wt, _ptr(chi2), _ptr(field)))
         else:
             st, keep_i = self._instrument('fit_field_chi2', instrument, head[6])

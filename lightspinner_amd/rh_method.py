@@ -504,7 +504,7 @@ class Context:
         pick = (lambda a: a[0, 0]) if scalar else (lambda a: a[0])
         return DepthRays(r.mus, r.la0, **{w: pick(getattr(r, w)) for w in DepthRays.FIELDS})
 
-    def compute_stokes(self, mus, B, gammaB, chiB, transition=None, la0=0, nla=None, instrument=None):
+    def compute_stokes(self, mus, B, gammaB, chiB, transition=None, la0=0, nla=None, instrument=None, vlos=None):
         """Emergent Stokes spectra I, Q, U, V in a magnetic field (Zeeman effect) by the field-free method: these populations and
         this J, one polarised formal solution (DELO-linear) along the rays with direction cosines `mus`.  B [T], gammaB, chiB [rad]:
         [Nspace] or scalars -- strength, inclination against the vertical, azimuth; +Q lies along the projection of the vertical
@@ -513,6 +513,8 @@ class Context:
         levels' J, L, S); a line without either stays unpolarised.  transition: one of the context's transitions (the object, or its
         place in [t for atom in activeAtoms for t in atom.trans]) selects that transition's own window, as in compute_depth_rays.
         instrument: a fit.Instrument over the window's wavelengths: the spectra as it sees them, [nobs][nmu] (Engine.apply_instrument).
+        vlos [m/s], a scalar or [Nspace]: the line-of-sight velocity of this call in the place of the atmosphere's, with its sign
+        convention (include/lsx_hip_stokes_velocity.h).  Populations and J stay the context's: they do not follow it.
         -> an object with .I .Q .U .V, each [nla][nmu] ([nla] for a float mu), .mus, .la0.  Nothing of the context changes."""
         from . import zeeman
         from .problem import StokesRays
@@ -524,7 +526,8 @@ class Context:
             la0, nla = int(transition.Nblue), int(transition.wavelength.shape[0])
         patterns = [zeeman.zeeman_components(t.transModel) for a in self.activeAtoms for t in a.trans if t.isLine]
         scalar = np.ndim(mus) == 0
-        r = self._engine.stokes_rays(np.atleast_1d(np.asarray(mus, dtype=np.float64)), B, gammaB, chiB, patterns=patterns, la0=la0, nla=nla)
+        r = self._engine.stokes_rays(np.atleast_1d(np.asarray(mus, dtype=np.float64)), B, gammaB, chiB, patterns=patterns, la0=la0, nla=nla,
+                                     vlos=vlos)
         pick = (lambda a: a[0, :, 0]) if scalar else (lambda a: a[0])
         if instrument is not None:
             seen = self._engine.apply_instrument(np.stack([getattr(r, w) for w in StokesRays.FIELDS], axis=1), instrument)
@@ -532,12 +535,14 @@ class Context:
         return StokesRays(r.mus, r.la0, *(pick(getattr(r, w)) for w in StokesRays.FIELDS))
 
     def compute_stokes_response(self, mus, B, gammaB, chiB, transition=None, la0=0, nla=None, parameters=('B', 'gammaB', 'chiB'),
-                                amplitudes=None, ks=None):
+                                amplitudes=None, ks=None, vlos=None):
         """Response functions of the emergent Stokes vector of compute_stokes to the field strength, inclination and azimuth at every
         depth: RF_p[k] = (S(p_k + a_p / 2) - S(p_k - a_p / 2)) / a_p, per tesla resp. per radian.  In the field-free method this
         is the change of one polarised formal solution: no NLTE solve (include/lsx_hip_stokes_response.h).  mus, B, gammaB, chiB,
         transition, la0, nla and the Zeeman patterns as in compute_stokes; parameters: some of 'B', 'gammaB', 'chiB'; amplitudes:
-        a dict from those names to a_p (default 1e-3 T, 1e-3 rad); ks: the depths (None: all).
+        a dict from those names to a_p (default 1e-3 T, 1e-3 rad); ks: the depths (None: all).  vlos as in compute_stokes; 'vlos'
+        may then be among the parameters (per m/s, default amplitude 100 m/s), and where it is requested without a velocity the
+        atmosphere's own vlos is the velocity of the call.
         -> an object with .rf[name], each [4][nla][nk][nmu] ([4][nla][nk] for a float mu), .stokes (what compute_stokes returns),
         .ks, .mus, .la0, .amplitudes.  Nothing of the context changes."""
         from . import zeeman
@@ -550,11 +555,19 @@ class Context:
             la0, nla = int(transition.Nblue), int(transition.wavelength.shape[0])
         patterns = [zeeman.zeeman_components(t.transModel) for a in self.activeAtoms for t in a.trans if t.isLine]
         scalar = np.ndim(mus) == 0
+        if vlos is None and 'vlos' in ([parameters] if isinstance(parameters, str) else list(parameters)):
+            vlos = self._atmos_vlos()
         r = self._engine.stokes_response(np.atleast_1d(np.asarray(mus, dtype=np.float64)), B, gammaB, chiB, patterns=patterns, la0=la0,
-                                         nla=nla, parameters=parameters, amplitudes=amplitudes, ks=ks)
+                                         nla=nla, parameters=parameters, amplitudes=amplitudes, ks=ks, vlos=vlos)
         pick = (lambda a: a[0, :, 0]) if scalar else (lambda a: a[0])
         stokes = StokesRays(r.mus, r.la0, *(pick(getattr(r.stokes, w)) for w in StokesRays.FIELDS))
         return StokesResponse({w: (a[0, ..., 0] if scalar else a[0]) for w, a in r.rf.items()}, stokes, r.ks, r.mus, r.la0, r.amplitudes)
+
+    def _atmos_vlos(self):
+        """the atmosphere's line-of-sight velocity [Nspace] (zeros where it has none)"""
+        Ns = self._engine.problem.Nspace
+        v = getattr(self.atmos, 'vlos', None)
+        return np.zeros(Ns) if v is None else np.broadcast_to(np.asarray(v, dtype=np.float64), (Ns,)).copy()
 
     def fit_field(self, mus, obs, transition=None, basis=None, start=None, nnode=None, weight=None, base=None, la0=0, nla=None,
                   amplitudes=None, instrument=None, **loop):
@@ -565,6 +578,9 @@ class Context:
         weight as obs or None; base [3][Nspace] or None; mus, transition, la0, nla and the Zeeman patterns as in compute_stokes;
         amplitudes as in compute_stokes_response; instrument: a fit.Instrument over the window's wavelengths, then obs and weight are
         [4][nobs][nmu]; **loop: lo, hi, lambda0, factor, lambda_min, lambda_max, tol, max_iter, log.
+        With 'vlos' rows in the basis dict (or nnode of four counts) the line-of-sight velocity [m/s] is fitted with the field
+        (include/lsx_hip_stokes_velocity.h): vlos = base_3 + its nodes' expansion, base [4][Nspace]; base None: zeros for the field and
+        the atmosphere's vlos for the velocity.  Populations and J do not follow the velocity.  .field has 4 rows.
         -> fit.FieldFit without the column axis.  Nothing of the context changes."""
         from . import zeeman
         from .drivers import fit_field_columns
@@ -579,6 +595,9 @@ class Context:
             basis, nnode = stack_basis(**basis)
         if basis is None or start is None or nnode is None:
             raise ValueError('fit_field: basis (with nnode, or as a dict per parameter) and start are needed')
+        if len(nnode) == 4 and base is None:
+            base = np.zeros((4, self._engine.problem.Nspace))
+            base[3] = self._atmos_vlos()
         patterns = [zeeman.zeeman_components(t.transModel) for a in self.activeAtoms for t in a.trans if t.isLine]
         mu = np.atleast_1d(np.asarray(mus, dtype=np.float64))
         nla_ = self._engine.problem.Nspect - int(la0) if nla is None else int(nla)
