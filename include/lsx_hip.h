@@ -84,6 +84,7 @@ int lsx_hip_poison_lds(int32_t device, int32_t rounds);
 #include "lsx_hip_stokes.h"
 #include "lsx_hip_stokes_response.h"
 #include "lsx_hip_fit.h"
+#include "lsx_hip_fit_regular.h"
 #include "lsx_hip_stokes_velocity.h"
 
 #endif /* LSX_HIP_H */

@@ -28,6 +28,10 @@ class LsxFitInstrument(C.Structure):            # include/lsx_hip_fit.h
     _fields_ = [('nobs', C.c_int32), ('width', C.c_int32), ('first', C.POINTER(C.c_int32)), ('weight', _dp)]
 
 
+class LsxFitPenalty(C.Structure):               # include/lsx_hip_fit_regular.h
+    _fields_ = [('nrow', C.c_int32), ('L', _dp), ('target', _dp)]
+
+
 class LsxTransition(C.Structure):
     _fields_ = [('atom', C.c_int32), ('is_line', C.c_int32), ('i', C.c_int32), ('j', C.c_int32),
                 ('Nblue', C.c_int32), ('Nlambda', C.c_int32),
@@ -301,6 +305,15 @@ class LsxLibrary:
             d.lsx_hip_velocity_fit_normal.restype = C.c_int
             d.lsx_hip_velocity_fit_chi2.argtypes = head + [_dp, _dp, _dp, _dp, inst]
             d.lsx_hip_velocity_fit_chi2.restype = C.c_int
+        self.has_fit_regular = hasattr(d, 'lsx_hip_regular_penalty')    # include/lsx_hip_fit_regular.h
+        if self.has_fit_regular:
+            ip32 = C.POINTER(C.c_int32)
+            pen = C.POINTER(LsxFitPenalty)
+            d.lsx_hip_regular_penalty.argtypes = [C.c_void_p, C.c_int32, C.c_int32, pen, _dp, _dp, _dp, _dp, _dp]
+            d.lsx_hip_regular_penalty.restype = C.c_int
+            d.lsx_hip_regular_uncertainty.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _dp, pen, _dp, C.c_int32, ip32, _dp, C.c_int32,
+                                                      _dp, _dp, _dp, _dp, ip32]
+            d.lsx_hip_regular_uncertainty.restype = C.c_int
         self.has_background = hasattr(d, 'lsx_hip_background')         # include/lsx_hip_background.h
         if self.has_background:
             ip32 = C.POINTER(C.c_int32)

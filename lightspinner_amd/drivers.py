@@ -296,7 +296,8 @@ def advance_time_columns(engine, dt, nsteps=1, dJ_tol=2e-3, dPops_tol=1e-3, max_
 
 
 def fit_field_columns(backend, obs, mus, basis, nodes0, nnode, weight=None, base=None, lo=None, hi=None, lambda0=1e-2, factor=10.0,
-                      lambda_min=1e-9, lambda_max=1e8, tol=1e-12, max_iter=30, log=None, **call):
+                      lambda_min=1e-9, lambda_max=1e8, tol=1e-12, max_iter=30, log=None, penalty=None, uncertainty=False, scale=None,
+                      **call):
     """Levenberg-Marquardt fit of the field vector of many independent columns to observed Stokes profiles (include/lsx_hip_fit.h).
     backend: anything with fit_field_normal, fit_field_chi2 and fit_field_step as Engine has them (an Engine is one).  obs
     [ncol][4][nla][nmu]; basis [P][Nspace], nnode, nodes0 [ncol][P], weight, base as in Engine.fit_field_normal; lo, hi [P]: bounds
@@ -305,8 +306,19 @@ def fit_field_columns(backend, obs, mus, basis, nodes0, nnode, weight=None, base
     fell the trial is accepted and lambda /= factor (not below lambda_min), otherwise lambda *= factor.  A column is done when a
     trial moved chi2 by less than tol x the chi2 the column started from (the trial is still accepted if it is lower), when lambda
     passes lambda_max, or at max_iter; a done column is frozen: its nodes no longer move.  This loop compares and scales scalars;
-    every sum and every solve is the backend's.  -> fit.FieldFit."""
+    every sum and every solve is the backend's.
+    penalty: a fit.Penalty (include/lsx_hip_fit_regular.h): every normal-equation call and every chi2 call is followed by
+    backend.fit_field_penalty, and the loop minimises data + penalty (.chi2, .history); .chi2_data and .penalty are the two parts.
+    uncertainty=True: after the loop one more fit_field_normal at the final nodes, then backend.fit_field_uncertainty on the data's
+    hess (with the penalty: the sandwich) -> .uncertainty.  scale: what the covariance is multiplied by -- None, [ncol], or 'reduced':
+    chi2_data / (N - P) with N the column's points of positive weight (a column with N <= P has no estimate: NaN, status 1); a scale
+    without uncertainty=True is refused.
+    Without the two the backend sees the calls it ever saw.  -> fit.FieldFit."""
     from .fit import CONVERGED, LAMBDA_CEILING, MAX_ITER, FieldFit
+    if isinstance(scale, str) and (scale != 'reduced' or obs is None):
+        raise ValueError("fit_field_columns: scale is None, an array [ncol] or 'reduced' (which needs obs)")
+    if scale is not None and not uncertainty:
+        raise ValueError('fit_field_columns: scale multiplies the covariance: it goes with uncertainty=True')
     nodes = np.array(np.atleast_2d(np.asarray(nodes0, dtype=np.float64)), dtype=np.float64)
     ncol = nodes.shape[0]
     chi2_call = {k: v for k, v in call.items() if k != 'amplitudes'}
@@ -316,15 +328,26 @@ def fit_field_columns(backend, obs, mus, basis, nodes0, nnode, weight=None, base
     iterations = np.zeros(ncol, dtype=np.int64)
     chi2, field = backend.fit_field_chi2(mus, basis, nnode, nodes, obs, weight=weight, base=base, **chi2_call)
     chi2 = np.array(chi2, dtype=np.float64)
+    chi2_data, pen = chi2, None
+    if penalty is not None:
+        chi2_data = chi2.copy()
+        chi2, _, _, pen = backend.fit_field_penalty(nodes, penalty, chi2_data)
+        chi2, pen = np.array(chi2, dtype=np.float64), np.array(pen, dtype=np.float64)
     first = chi2.copy()
     history = [chi2.copy()]
     for it in range(1, int(max_iter) + 1):
         if not active.any():
             break
         ne = backend.fit_field_normal(mus, basis, nnode, nodes, obs, weight=weight, base=base, **call)
-        trial, _, st = backend.fit_field_step(ne.hess, ne.grad, lam, nodes, lo, hi)
+        grad, hess = ne.grad, ne.hess
+        if penalty is not None:
+            _, grad, hess, _ = backend.fit_field_penalty(nodes, penalty, ne.chi2, ne.grad, ne.hess)
+        trial, _, st = backend.fit_field_step(hess, grad, lam, nodes, lo, hi)
         trial = np.where(active[:, None], trial, nodes)               # a frozen column is asked about its own nodes
         c_trial, f_trial = backend.fit_field_chi2(mus, basis, nnode, trial, obs, weight=weight, base=base, **chi2_call)
+        if penalty is not None:
+            d_trial = np.array(c_trial, dtype=np.float64)
+            c_trial, _, _, p_trial = backend.fit_field_penalty(trial, penalty, d_trial)
         with np.errstate(invalid='ignore'):
             accept = active & (st == 0) & (c_trial < chi2)
             settled = active & (st == 0) & (np.abs(c_trial - chi2) < tol * first)
@@ -332,6 +355,9 @@ def fit_field_columns(backend, obs, mus, basis, nodes0, nnode, weight=None, base
         nodes[accept] = trial[accept]
         field[accept] = f_trial[accept]
         chi2[accept] = c_trial[accept]
+        if penalty is not None:
+            chi2_data[accept] = d_trial[accept]
+            pen[accept] = p_trial[accept]
         lam = np.where(accept, np.maximum(lam / factor, lambda_min), np.where(active, lam * factor, lam))
         settled |= active & (chi2 == 0.0)
         ceiling = active & ~settled & (lam > lambda_max)
@@ -341,4 +367,37 @@ def fit_field_columns(backend, obs, mus, basis, nodes0, nnode, weight=None, base
         history.append(chi2.copy())
         if log:
             log('Fit iteration %.3d: %d of %d columns still iterating, largest chi2 %.6e' % (it, int(active.sum()), ncol, float(chi2.max())))
-    return FieldFit(nodes, field, chi2, np.array(history), lam, iterations, status, nnode)
+    # the degrees of freedom: a count of the points of positive weight, no sum over the data -- made when it is asked for (FieldFit.dof),
+    # so that a fit without the new arguments does no more on the host than it ever did
+    def count_dof():
+        if obs is None:
+            return None
+        shape = np.shape(obs)
+        if weight is None:
+            return np.full(ncol, int(np.prod(shape[1:]))) - nodes.shape[1]
+        try:
+            positive = np.broadcast_to(np.asarray(weight), shape).reshape(ncol, -1) > 0
+        except ValueError:                # a weight of another shape is the backend's to judge
+            return None
+        return np.count_nonzero(positive, axis=1) - nodes.shape[1]
+
+    dof = count_dof
+    unc = None
+    if uncertainty:
+        s = scale
+        none = np.zeros(ncol, dtype=bool)
+        if isinstance(scale, str):        # 'reduced'
+            dof = count_dof()
+            if dof is None:
+                raise ValueError("fit_field_columns: scale='reduced' needs a weight of the shape of obs (or None)")
+            none = dof <= 0
+            s = np.where(none, 1.0, chi2_data / np.where(none, 1, dof))
+        ne = backend.fit_field_normal(mus, basis, nnode, nodes, obs, weight=weight, base=base, **call)
+        unc = backend.fit_field_uncertainty(ne.hess, basis, nnode, penalty=penalty, scale=s)
+        if none.any():                    # no estimate of the scale: no uncertainty
+            for a in (unc.ainv, unc.cov, unc.sigma, unc.field_sigma):
+                if a is not None:
+                    a[none] = np.nan
+            unc.status[none] = 1
+    return FieldFit(nodes, field, chi2, np.array(history), lam, iterations, status, nnode, penalty=pen, chi2_data=chi2_data,
+                    uncertainty=unc, dof=dof)

@@ -891,6 +891,75 @@ class Engine:
                                                            _ptr(trial), _ptr(pred), status.ctypes.data_as(C.POINTER(C.c_int32))))
         return trial, pred, status
 
+    def _penalty(self, who, penalty, ncol, P, with_target=True):
+        """-> (the C struct of a fit.Penalty, what must outlive the call)"""
+        from . import _capi
+        if not getattr(self.lib, 'has_fit_regular', False):
+            raise NotImplementedError('%s (%s) does not export lsx_hip_regular_penalty: %s is computed by the HIP library only'
+                                      % (self.lib.path, self.lib.backend, who))
+        if penalty.nparam != P:
+            raise ValueError('%s: the penalty is made for %d node values, the call has %d' % (who, penalty.nparam, P))
+        L = f64(penalty.L)
+        tg = penalty.targets(ncol) if with_target else None
+        return _capi.LsxFitPenalty(penalty.nrow, _ptr(L), None if tg is None else _ptr(tg)), (L, tg)
+
+    def fit_field_penalty(self, nodes, penalty, chi2, grad=None, hess=None):
+        """The penalty of a regularised fit added to what fit_field_normal / fit_field_chi2 returned for `nodes` [ncol][P]
+        (include/lsx_hip_fit_regular.h, lsx_hip_regular_penalty): penalty a fit.Penalty; chi2 [ncol], grad [ncol][P], hess [ncol][P][P]
+        (both or neither: without them the chi2 of a trial, the bits the full call gives).  The arguments are not changed.
+        -> (chi2 + penalty, grad + L^T rho or None, hess + L^T L or None, penalty [ncol]).  Only the HIP library computes it."""
+        x = f64(np.atleast_2d(np.asarray(nodes, dtype=np.float64)))
+        nc, P = x.shape
+        st, keep = self._penalty('fit_field_penalty', penalty, nc, P)
+        c = np.array(np.broadcast_to(np.asarray(chi2, dtype=np.float64), (nc,)), dtype=np.float64)
+        if (grad is None) != (hess is None):
+            raise ValueError('fit_field_penalty: grad and hess go together')
+        g = None if grad is None else np.array(np.asarray(grad, dtype=np.float64).reshape(nc, P), dtype=np.float64)
+        H = None if hess is None else np.array(np.asarray(hess, dtype=np.float64).reshape(nc, P, P), dtype=np.float64)
+        pen = np.empty(nc)
+        self.lib.check(self.lib.dll.lsx_hip_regular_penalty(self._h, nc, P, C.byref(st), _ptr(x), _ptr(c), None if g is None else _ptr(g),
+                                                            None if H is None else _ptr(H), _ptr(pen)))
+        del keep
+        return c, g, H, pen
+
+    def fit_field_uncertainty(self, hess, basis, nnode, penalty=None, scale=None, ainv=True, field_sigma=True):
+        """The uncertainties of the fitted nodes from the DATA's normal equations hess [ncol][P][P] at the solution
+        (include/lsx_hip_fit_regular.h, lsx_hip_regular_uncertainty): A = hess + L^T L of the fit.Penalty (None: hess), its inverse by
+        Cholesky on the device, cov = scale x ainv hess ainv (the sandwich; without a penalty ainv), sigma = sqrt(diag cov) and the
+        standard deviation of the expanded field at every depth from basis [P][Nspace] and nnode (three or four counts, any Nspace).
+        scale [ncol], a scalar, or None for 1.  -> fit.FieldUncertainty (.ainv and .field_sigma None if not asked for); a column whose
+        system is singular or holds a NaN has status 1 and NaN everywhere.  Only the HIP library computes it."""
+        from .fit import FieldUncertainty
+        H = f64(np.asarray(hess, dtype=np.float64))
+        if H.ndim == 2:
+            H = H[None]
+        if H.ndim != 3 or H.shape[1] != H.shape[2]:
+            raise ValueError('fit_field_uncertainty: hess must be [ncol][P][P]')
+        nc, P = H.shape[:2]
+        nn = np.ascontiguousarray(np.asarray(nnode).reshape(-1), dtype=np.int32)
+        bas = f64(np.atleast_2d(np.asarray(basis, dtype=np.float64)))
+        if bas.shape[0] != P:
+            raise ValueError('fit_field_uncertainty: basis has %d rows, hess is %d x %d' % (bas.shape[0], P, P))
+        Ns = bas.shape[1]
+        if penalty is None:
+            if not getattr(self.lib, 'has_fit_regular', False):
+                raise NotImplementedError('%s (%s) does not export lsx_hip_regular_uncertainty: the uncertainties of a fit are computed '
+                                          'by the HIP library only' % (self.lib.path, self.lib.backend))
+            st, keep = None, None
+        else:
+            st, keep = self._penalty('fit_field_uncertainty', penalty, nc, P, with_target=False)
+        sc = None if scale is None else f64(np.broadcast_to(np.asarray(scale, dtype=np.float64), (nc,)))
+        ai = np.empty((nc, P, P)) if ainv else None
+        cov, sigma, status = np.empty((nc, P, P)), np.empty((nc, P)), np.empty(nc, dtype=np.int32)
+        fs = np.empty((nc, nn.shape[0], Ns)) if field_sigma else None
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        self.lib.check(self.lib.dll.lsx_hip_regular_uncertainty(self._h, nc, P, _ptr(H), None if st is None else C.byref(st),
+                                                                None if sc is None else _ptr(sc), nn.shape[0], ip(nn), _ptr(bas), Ns,
+                                                                None if ai is None else _ptr(ai), _ptr(cov), _ptr(sigma),
+                                                                None if fs is None else _ptr(fs), ip(status)))
+        del keep
+        return FieldUncertainty(ai, cov, sigma, fs, status, nn)
+
     def _background_lib(self, entry):
         if not getattr(self.lib, 'has_background', False):
             raise NotImplementedError('%s (%s) does not export %s: the equation of state and the background opacity are computed '

@@ -577,14 +577,16 @@ class Context:
         (B, gammaB, chiB), or a dict from those names to row sets (fit.hat_basis makes them); start: the first node values [P];
         weight as obs or None; base [3][Nspace] or None; mus, transition, la0, nla and the Zeeman patterns as in compute_stokes;
         amplitudes as in compute_stokes_response; instrument: a fit.Instrument over the window's wavelengths, then obs and weight are
-        [4][nobs][nmu]; **loop: lo, hi, lambda0, factor, lambda_min, lambda_max, tol, max_iter, log.
+        [4][nobs][nmu]; **loop: lo, hi, lambda0, factor, lambda_min, lambda_max, tol, max_iter, log, and penalty (a fit.Penalty:
+        the regularised fit), uncertainty (True: .uncertainty holds the nodes' covariance and the field's error band) and scale
+        (None, a number or 'reduced'), as drivers.fit_field_columns takes them (include/lsx_hip_fit_regular.h).
         With 'vlos' rows in the basis dict (or nnode of four counts) the line-of-sight velocity [m/s] is fitted with the field
         (include/lsx_hip_stokes_velocity.h): vlos = base_3 + its nodes' expansion, base [4][Nspace]; base None: zeros for the field and
         the atmosphere's vlos for the velocity.  Populations and J do not follow the velocity.  .field has 4 rows.
         -> fit.FieldFit without the column axis.  Nothing of the context changes."""
         from . import zeeman
         from .drivers import fit_field_columns
-        from .fit import FieldFit, stack_basis
+        from .fit import FieldFit, FieldUncertainty, stack_basis
         self._cancel_lookahead()                  # (the library's J is the last accepted call's again)
         self._push_host_edits()
         if transition is not None:
@@ -610,7 +612,12 @@ class Context:
                                   (1, 4, npix, -1) if np.ndim(weight) else ()), shape),
                               base=None if base is None else np.asarray(base, dtype=np.float64)[None], patterns=patterns, la0=la0, nla=nla_,
                               amplitudes=amplitudes, **loop)
-        return FieldFit(r.nodes[0], r.field[0], r.chi2[0], r.history[:, 0], r.lam[0], r.iterations[0], r.status[0], r.nnode)
+        u = r.uncertainty
+        if u is not None:
+            u = FieldUncertainty(None if u.ainv is None else u.ainv[0], u.cov[0], u.sigma[0],
+                                 None if u.field_sigma is None else u.field_sigma[0], u.status[0], u.nnode)
+        return FieldFit(r.nodes[0], r.field[0], r.chi2[0], r.history[:, 0], r.lam[0], r.iterations[0], r.status[0], r.nnode,
+                        penalty=r.penalty[0], chi2_data=r.chi2_data[0], uncertainty=u, dof=lambda: None if r.dof is None else r.dof[0])
 
     def compute_rates(self):
         """Radiative rates of every transition (rh_method.py:691-692) as ONE formal solution gives them from these populations and
