@@ -122,6 +122,80 @@ REQUIRED_SYMBOLS = (
     'lsx_sync_begin_populations', 'lsx_fetch_populations', 'lsx_build_id',
 )
 
+# ---- the entries of the HIP library alone (include/lsx_hip*.h): bound where the library has them, never required ----
+_ctx, _i32, _sz, _ip = C.c_void_p, C.c_int32, C.c_size_t, C.POINTER(C.c_int32)
+_inst, _pen, _eos = C.POINTER(LsxFitInstrument), C.POINTER(LsxFitPenalty), C.POINTER(LsxEosTables)
+_WORK_CAP = [_ctx, _sz]                                        # lsx_hip_*_work_cap(ctx, nbytes)
+_RAYS = [_ctx, _i32, _dp, _i32, _i32, _i32, _i32]             # ctx, nmu, mu, col0, ncol, la0, nla
+_STOKES = _RAYS + [_dp, _dp, _dp, _ip, _ip, _dp, _dp]          # ... B, gammaB, chiB, ncomp, alpha, strength, shift
+_STOKES_RAYS = _STOKES + [_dp, _sz]                            # ... dst, nbytes
+_RESPONSE = _STOKES + [C.c_uint32, _dp, _i32, _ip, _dp, _sz, _dp, _sz]      # ... parameters, amplitude, nk, ks, rf, bytes, stokes, bytes
+_FIT = _RAYS + [_ip, _ip, _dp, _dp, _ip, _dp, _dp, _dp]        # ... ncomp, alpha, strength, shift, nnode, basis, base, nodes
+_NORMAL, _CHI2 = _FIT + [_dp] * 7, _FIT + [_dp] * 4            # ... (amplitude,) obs, weight, chi2, (grad, hess,) field
+
+# feature -> (what the NotImplementedError of a library without it says, its entries as (symbol, argtypes)).  LsxLibrary has
+# `has_<feature>` for each: whether the library exports the feature's FIRST entry.  A new entry family is a new row here.
+HIP_FEATURES = {
+    'emergent_rays': ('emergent spectra at arbitrary angles are computed by the HIP library only', [
+        ('lsx_hip_emergent_rays', [_ctx, _i32, _dp, _i32, _i32, _dp, _sz])]),
+    'radiative_rates': ('radiative rates are computed by the HIP library only', [
+        ('lsx_hip_radiative_rates', [_ctx, _i32, _i32, _dp, _dp, _dp, _sz]),
+        ('lsx_hip_radiative_rates_work_cap', _WORK_CAP)]),
+    'radiative_losses': ('radiative losses are computed by the HIP library only', [
+        ('lsx_hip_radiative_losses', [_ctx, _i32, _i32] + [_dp] * 6 + [_sz] * 3),
+        ('lsx_hip_radiative_losses_work_cap', _WORK_CAP),
+        ('lsx_hip_frequency_weights', [_i32, _dp, _dp])]),
+    'depth_rays': ('the depth-resolved final pass is computed by the HIP library only', [
+        ('lsx_hip_depth_rays', _RAYS + [_dp] * 6 + [_sz, _sz]),
+        ('lsx_hip_depth_rays_work_cap', _WORK_CAP)]),
+    'spectrum': ('emergent spectra at arbitrary wavelengths are computed by the HIP library only', [
+        ('lsx_hip_spectrum', [_ctx, _i32] + [_dp] * 5 + [_i32, _dp, _i32, _i32, _dp, _sz]),
+        ('lsx_hip_spectrum_work_cap', _WORK_CAP)]),
+    'stokes': ('polarised spectra are computed by the HIP library only', [
+        ('lsx_hip_stokes_rays', _STOKES_RAYS),
+        ('lsx_hip_stokes_rays_work_cap', _WORK_CAP)]),
+    'stokes_response': ('polarised spectra and their response functions are computed by the HIP library only', [
+        ('lsx_hip_response_stokes', _RESPONSE),
+        ('lsx_hip_response_stokes_work_cap', _WORK_CAP)]),
+    'fit_field': ('the field fit is computed by the HIP library only', [
+        ('lsx_hip_fit_field_normal', _NORMAL),
+        ('lsx_hip_fit_field_chi2', _CHI2),
+        ('lsx_hip_fit_field_step', [_ctx, _i32, _i32] + [_dp] * 8 + [_ip]),
+        ('lsx_hip_fit_field_work_cap', _WORK_CAP)]),
+    'fit_instrument': ('the instrument of a fit is applied by the HIP library only', [
+        ('lsx_hip_instrument_fit_normal', _NORMAL + [_inst]),
+        ('lsx_hip_instrument_fit_chi2', _CHI2 + [_inst]),
+        ('lsx_hip_instrument_apply', [_ctx, _inst, _i32, _i32, _i32, _dp, _dp])]),
+    'stokes_velocity': ('a line-of-sight velocity per call is taken by the HIP library only', [
+        ('lsx_hip_velocity_stokes_rays', _STOKES_RAYS + [_dp]),
+        ('lsx_hip_velocity_response_stokes', _RESPONSE + [_dp]),
+        ('lsx_hip_velocity_fit_normal', _NORMAL + [_inst]),
+        ('lsx_hip_velocity_fit_chi2', _CHI2 + [_inst])]),
+    'fit_regular': ('the penalty and the uncertainties of a fit are computed by the HIP library only', [
+        ('lsx_hip_regular_penalty', [_ctx, _i32, _i32, _pen] + [_dp] * 5),
+        ('lsx_hip_regular_uncertainty', [_ctx, _i32, _i32, _dp, _pen, _dp, _i32, _ip, _dp, _i32, _dp, _dp, _dp, _dp, _ip])]),
+    'background': ('the equation of state and the background opacity are computed by the HIP library only', [
+        ('lsx_hip_background', [_ctx, _eos, _i32, _i32, _dp, _dp, _dp, _i32, _dp, _dp, _dp, _dp, _i32]),
+        ('lsx_hip_eos', [_ctx, _eos, _i32] + [_dp] * 5 + [_ip])]),
+    'scales': ('the depth scales are converted by the HIP library only', [
+        ('lsx_hip_convert_scales', [_ctx, _eos, _i32, _i32, _i32, _dp, _dp, _dp, _dp, C.c_double, _dp, _dp, _dp, _dp, _i32])]),
+    'eq_pops': ('the LTE populations are computed by the HIP library only', [
+        ('lsx_hip_eq_pops', [_ctx, _i32, C.POINTER(LsxEqAtom), _i32] + [_dp] * 5)]),
+    'ng': ('Ng acceleration is done by the HIP library only', [
+        ('lsx_hip_ng_configure', [_ctx, _i32, _i32]),
+        ('lsx_hip_ng_state', [_ctx, _i32, _i32, _ip, _ip, _ip, _dp])]),
+    'time_dep': ('the time-dependent step is taken by the HIP library only', [
+        ('lsx_hip_time_dep_start', [_ctx, _i32, _i32, _dp, _dp]),
+        ('lsx_hip_time_dep_update_async', [_ctx]),
+        ('lsx_hip_time_dep_update', [_ctx, _dp]),
+        ('lsx_hip_time_dep_state', [_ctx, _i32, _i32, _dp, _dp])]),
+    'boundary': ("boundary conditions other than the reference's are set in the HIP library only", [
+        ('lsx_hip_set_boundary', [_ctx, _i32, _i32, _i32, _i32, _dp, _dp]),
+        ('lsx_hip_boundary_state', [_ctx, _i32, _i32, _ip])]),
+    'epilogue_info': ('the launch counters of the epilogue are kept by the HIP library only', [
+        ('lsx_hip_epilogue_info', [_ctx, C.POINTER(C.c_int64)])]),
+}
+
 
 class LsxError(RuntimeError):
     def __init__(self, code, msg):
@@ -136,6 +210,16 @@ class LsxSingularError(LsxError, np.linalg.LinAlgError):
 
 def _ptr(a):
     return a.ctypes.data_as(_dp)
+
+
+def _iptr(a):
+    """an int32 array"""
+    return a.ctypes.data_as(_ip)
+
+
+def _opt(a):
+    """an optional float64 array: None -> NULL"""
+    return None if a is None else _ptr(a)
 
 
 def f64(a, shape=None):
@@ -216,148 +300,22 @@ class LsxLibrary:
         d.lsx_time_formal_sol.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _dp, _dp]
         d.lsx_algorithmic_bytes_per_column.argtypes = [C.c_void_p]
         d.lsx_algorithmic_bytes_per_column.restype = C.c_double
-        # entries of the HIP library alone (include/lsx_hip.h): bound where the library has them, never required
-        self.has_emergent_rays = hasattr(d, 'lsx_hip_emergent_rays')
-        if self.has_emergent_rays:
-            d.lsx_hip_emergent_rays.argtypes = [C.c_void_p, C.c_int32, _dp, C.c_int32, C.c_int32, _dp, C.c_size_t]
-            d.lsx_hip_emergent_rays.restype = C.c_int
-        self.has_radiative_rates = hasattr(d, 'lsx_hip_radiative_rates')
-        if self.has_radiative_rates:
-            d.lsx_hip_radiative_rates.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _dp, _dp, _dp, C.c_size_t]
-            d.lsx_hip_radiative_rates.restype = C.c_int
-            d.lsx_hip_radiative_rates_work_cap.argtypes = [C.c_void_p, C.c_size_t]
-            d.lsx_hip_radiative_rates_work_cap.restype = C.c_int
-        self.has_radiative_losses = hasattr(d, 'lsx_hip_radiative_losses')      # include/lsx_hip_losses.h
-        if self.has_radiative_losses:
-            d.lsx_hip_radiative_losses.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp,
-                                                   C.c_size_t, C.c_size_t, C.c_size_t]
-            d.lsx_hip_radiative_losses.restype = C.c_int
-            d.lsx_hip_radiative_losses_work_cap.argtypes = [C.c_void_p, C.c_size_t]
-            d.lsx_hip_radiative_losses_work_cap.restype = C.c_int
-            d.lsx_hip_frequency_weights.argtypes = [C.c_int32, _dp, _dp]
-            d.lsx_hip_frequency_weights.restype = C.c_int
-        self.has_depth_rays = hasattr(d, 'lsx_hip_depth_rays')         # include/lsx_hip_depth.h
-        if self.has_depth_rays:
-            d.lsx_hip_depth_rays.argtypes = [C.c_void_p, C.c_int32, _dp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                                             _dp, _dp, _dp, _dp, _dp, _dp, C.c_size_t, C.c_size_t]
-            d.lsx_hip_depth_rays.restype = C.c_int
-            d.lsx_hip_depth_rays_work_cap.argtypes = [C.c_void_p, C.c_size_t]
-            d.lsx_hip_depth_rays_work_cap.restype = C.c_int
-        self.has_spectrum = hasattr(d, 'lsx_hip_spectrum')             # include/lsx_hip_spectrum.h
-        if self.has_spectrum:
-            d.lsx_hip_spectrum.argtypes = [C.c_void_p, C.c_int32, _dp, _dp, _dp, _dp, _dp, C.c_int32, _dp, C.c_int32, C.c_int32,
-                                           _dp, C.c_size_t]
-            d.lsx_hip_spectrum.restype = C.c_int
-            d.lsx_hip_spectrum_work_cap.argtypes = [C.c_void_p, C.c_size_t]
-            d.lsx_hip_spectrum_work_cap.restype = C.c_int
-        self.has_stokes = hasattr(d, 'lsx_hip_stokes_rays')            # include/lsx_hip_stokes.h
-        if self.has_stokes:
-            ip32 = C.POINTER(C.c_int32)
-            d.lsx_hip_stokes_rays.argtypes = [C.c_void_p, C.c_int32, _dp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp,
-                                              ip32, ip32, _dp, _dp, _dp, C.c_size_t]
-            d.lsx_hip_stokes_rays.restype = C.c_int
-            d.lsx_hip_stokes_rays_work_cap.argtypes = [C.c_void_p, C.c_size_t]
-            d.lsx_hip_stokes_rays_work_cap.restype = C.c_int
-        self.has_stokes_response = hasattr(d, 'lsx_hip_response_stokes')      # include/lsx_hip_stokes_response.h
-        if self.has_stokes_response:
-            ip32 = C.POINTER(C.c_int32)
-            d.lsx_hip_response_stokes.argtypes = [C.c_void_p, C.c_int32, _dp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp,
-                                                  ip32, ip32, _dp, _dp, C.c_uint32, _dp, C.c_int32, ip32, _dp, C.c_size_t, _dp, C.c_size_t]
-            d.lsx_hip_response_stokes.restype = C.c_int
-            d.lsx_hip_response_stokes_work_cap.argtypes = [C.c_void_p, C.c_size_t]
-            d.lsx_hip_response_stokes_work_cap.restype = C.c_int
-        self.has_fit_field = hasattr(d, 'lsx_hip_fit_field_normal')     # include/lsx_hip_fit.h
-        if self.has_fit_field:
-            ip32 = C.POINTER(C.c_int32)
-            head = [C.c_void_p, C.c_int32, _dp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, ip32, ip32, _dp, _dp, ip32, _dp, _dp, _dp]
-            d.lsx_hip_fit_field_normal.argtypes = head + [_dp, _dp, _dp, _dp, _dp, _dp, _dp]
-            d.lsx_hip_fit_field_normal.restype = C.c_int
-            d.lsx_hip_fit_field_chi2.argtypes = head + [_dp, _dp, _dp, _dp]
-            d.lsx_hip_fit_field_chi2.restype = C.c_int
-            d.lsx_hip_fit_field_step.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, ip32]
-            d.lsx_hip_fit_field_step.restype = C.c_int
-            d.lsx_hip_fit_field_work_cap.argtypes = [C.c_void_p, C.c_size_t]
-            d.lsx_hip_fit_field_work_cap.restype = C.c_int
-        self.has_fit_instrument = hasattr(d, 'lsx_hip_instrument_fit_normal')      # include/lsx_hip_fit_instrument.h
-        if self.has_fit_instrument:
-            ip32 = C.POINTER(C.c_int32)
-            inst = C.POINTER(LsxFitInstrument)
-            head = [C.c_void_p, C.c_int32, _dp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, ip32, ip32, _dp, _dp, ip32, _dp, _dp, _dp]
-            d.lsx_hip_instrument_fit_normal.argtypes = head + [_dp, _dp, _dp, _dp, _dp, _dp, _dp, inst]
-            d.lsx_hip_instrument_fit_normal.restype = C.c_int
-            d.lsx_hip_instrument_fit_chi2.argtypes = head + [_dp, _dp, _dp, _dp, inst]
-            d.lsx_hip_instrument_fit_chi2.restype = C.c_int
-            d.lsx_hip_instrument_apply.argtypes = [C.c_void_p, inst, C.c_int32, C.c_int32, C.c_int32, _dp, _dp]
-            d.lsx_hip_instrument_apply.restype = C.c_int
-        self.has_stokes_velocity = hasattr(d, 'lsx_hip_velocity_stokes_rays')      # include/lsx_hip_stokes_velocity.h
-        if self.has_stokes_velocity:
-            ip32 = C.POINTER(C.c_int32)
-            inst = C.POINTER(LsxFitInstrument)
-            d.lsx_hip_velocity_stokes_rays.argtypes = [C.c_void_p, C.c_int32, _dp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp,
-                                                       ip32, ip32, _dp, _dp, _dp, C.c_size_t, _dp]
-            d.lsx_hip_velocity_stokes_rays.restype = C.c_int
-            d.lsx_hip_velocity_response_stokes.argtypes = [C.c_void_p, C.c_int32, _dp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, _dp,
-                                                           _dp, ip32, ip32, _dp, _dp, C.c_uint32, _dp, C.c_int32, ip32, _dp, C.c_size_t, _dp,
-                                                           C.c_size_t, _dp]
-            d.lsx_hip_velocity_response_stokes.restype = C.c_int
-            head = [C.c_void_p, C.c_int32, _dp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, ip32, ip32, _dp, _dp, ip32, _dp, _dp, _dp]
-            d.lsx_hip_velocity_fit_normal.argtypes = head + [_dp, _dp, _dp, _dp, _dp, _dp, _dp, inst]
-            d.lsx_hip_velocity_fit_normal.restype = C.c_int
-            d.lsx_hip_velocity_fit_chi2.argtypes = head + [_dp, _dp, _dp, _dp, inst]
-            d.lsx_hip_velocity_fit_chi2.restype = C.c_int
-        self.has_fit_regular = hasattr(d, 'lsx_hip_regular_penalty')    # include/lsx_hip_fit_regular.h
-        if self.has_fit_regular:
-            ip32 = C.POINTER(C.c_int32)
-            pen = C.POINTER(LsxFitPenalty)
-            d.lsx_hip_regular_penalty.argtypes = [C.c_void_p, C.c_int32, C.c_int32, pen, _dp, _dp, _dp, _dp, _dp]
-            d.lsx_hip_regular_penalty.restype = C.c_int
-            d.lsx_hip_regular_uncertainty.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _dp, pen, _dp, C.c_int32, ip32, _dp, C.c_int32,
-                                                      _dp, _dp, _dp, _dp, ip32]
-            d.lsx_hip_regular_uncertainty.restype = C.c_int
-        self.has_background = hasattr(d, 'lsx_hip_background')         # include/lsx_hip_background.h
-        if self.has_background:
-            ip32 = C.POINTER(C.c_int32)
-            d.lsx_hip_eos.argtypes = [C.c_void_p, C.POINTER(LsxEosTables), C.c_int32, _dp, _dp, _dp, _dp, _dp, ip32]
-            d.lsx_hip_eos.restype = C.c_int
-            d.lsx_hip_background.argtypes = [C.c_void_p, C.POINTER(LsxEosTables), C.c_int32, C.c_int32, _dp, _dp, _dp, C.c_int32, _dp,
-                                             _dp, _dp, _dp, C.c_int32]
-            d.lsx_hip_background.restype = C.c_int
-        self.has_scales = hasattr(d, 'lsx_hip_convert_scales')         # include/lsx_hip_scales.h
-        if self.has_scales:
-            d.lsx_hip_convert_scales.argtypes = [C.c_void_p, C.POINTER(LsxEosTables), C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp,
-                                                 C.c_double, _dp, _dp, _dp, _dp, C.c_int32]
-            d.lsx_hip_convert_scales.restype = C.c_int
-        self.has_eq_pops = hasattr(d, 'lsx_hip_eq_pops')               # include/lsx_hip_eqpops.h
-        if self.has_eq_pops:
-            d.lsx_hip_eq_pops.argtypes = [C.c_void_p, C.c_int32, C.POINTER(LsxEqAtom), C.c_int32, _dp, _dp, _dp, _dp, _dp]
-            d.lsx_hip_eq_pops.restype = C.c_int
-        self.has_ng = hasattr(d, 'lsx_hip_ng_configure')               # include/lsx_hip_ng.h
-        if self.has_ng:
-            ip32 = C.POINTER(C.c_int32)
-            d.lsx_hip_ng_configure.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
-            d.lsx_hip_ng_configure.restype = C.c_int
-            d.lsx_hip_ng_state.argtypes = [C.c_void_p, C.c_int32, C.c_int32, ip32, ip32, ip32, _dp]
-            d.lsx_hip_ng_state.restype = C.c_int
-        self.has_time_dep = hasattr(d, 'lsx_hip_time_dep_start')       # include/lsx_hip_timedep.h
-        if self.has_time_dep:
-            d.lsx_hip_time_dep_start.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _dp, _dp]
-            d.lsx_hip_time_dep_start.restype = C.c_int
-            d.lsx_hip_time_dep_update_async.argtypes = [C.c_void_p]
-            d.lsx_hip_time_dep_update_async.restype = C.c_int
-            d.lsx_hip_time_dep_update.argtypes = [C.c_void_p, _dp]
-            d.lsx_hip_time_dep_update.restype = C.c_int
-            d.lsx_hip_time_dep_state.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _dp, _dp]
-            d.lsx_hip_time_dep_state.restype = C.c_int
-        self.has_boundary = hasattr(d, 'lsx_hip_set_boundary')         # include/lsx_hip_boundary.h
-        if self.has_boundary:
-            d.lsx_hip_set_boundary.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, _dp]
-            d.lsx_hip_set_boundary.restype = C.c_int
-            d.lsx_hip_boundary_state.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
-            d.lsx_hip_boundary_state.restype = C.c_int
-        self.has_epilogue_info = hasattr(d, 'lsx_hip_epilogue_info')   # include/lsx_hip_epilogue.h
-        if self.has_epilogue_info:
-            d.lsx_hip_epilogue_info.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
-            d.lsx_hip_epilogue_info.restype = C.c_int32
+        self._bind_hip_features()
+
+    def _bind_hip_features(self):
+        for feature, (_, entries) in HIP_FEATURES.items():
+            setattr(self, 'has_' + feature, hasattr(self.dll, entries[0][0]))
+            if not getattr(self, 'has_' + feature):
+                continue
+            for symbol, argtypes in entries:
+                entry = getattr(self.dll, symbol)
+                entry.argtypes = argtypes
+                entry.restype = C.c_int32 if symbol == 'lsx_hip_epilogue_info' else C.c_int       # (its count of values, not a status)
+
+    def missing(self, feature, entry):
+        """the error of a call that needs `entry` of a HIP_FEATURES feature this library does not have.  Reads .path and .backend only:
+        Engine calls it on whatever stands in for a library"""
+        raise NotImplementedError('%s (%s) does not export %s: %s' % (self.path, self.backend, entry, HIP_FEATURES[feature][0]))
 
     @property
     def backend(self):

@@ -15,7 +15,12 @@ from typing import List, Optional
 import numpy as np
 
 from . import _capi
-from ._capi import f64, _ptr
+from ._capi import f64, _ptr, _iptr, _opt
+
+
+def _vector(a):
+    """a scalar or any array (viewing angles, wavelengths) -> float64 [n]"""
+    return f64(np.atleast_1d(np.asarray(a, dtype=np.float64)).reshape(-1))
 
 
 @dataclass
@@ -526,12 +531,38 @@ class Engine:
         self.lib.check(self.lib.dll.lsx_get(self._h, what, int(col0), int(ncol), _ptr(out), out.nbytes))
         return out
 
+    # -- the entries of the HIP library alone (include/lsx_hip*.h; _capi.HIP_FEATURES): what their wrappers below share --
+    def _need(self, feature, entry):
+        """NotImplementedError naming `entry` where the library (or what stands in for one) lacks the feature"""
+        if not getattr(self.lib, 'has_' + feature, False):
+            _capi.LsxLibrary.missing(self.lib, feature, entry)
+
+    def _work_cap(self, entry, nbytes):
+        if nbytes is not None:
+            self.lib.check(getattr(self.lib.dll, entry)(self._h, int(nbytes)))
+
+    def _columns(self, col0, ncol):
+        return self.ncol - int(col0) if ncol is None else int(ncol)
+
+    def _window(self, la0, nla):
+        return self.problem.Nspect - int(la0) if nla is None else int(nla)
+
+    def _per_depth(self, a, nc):
+        """a scalar, [Nspace] or [nc][Nspace] -> [nc][Nspace]"""
+        return f64(np.broadcast_to(np.asarray(a, dtype=np.float64), (nc, self.problem.Nspace)))
+
+    @staticmethod
+    def _amplitudes(nq, amplitudes):
+        """-> (the amplitude of every parameter by name, those of the first nq of B, gammaB, chiB, vlos as the array the entries take)"""
+        amps = dict(StokesResponse.VELOCITY_DEFAULT_AMPLITUDES if nq == 4 else StokesResponse.DEFAULT_AMPLITUDES)
+        amps.update(amplitudes or {})
+        return amps, f64(np.array([amps[w] for w in StokesResponse.VELOCITY_PARAMETERS[:nq]], dtype=np.float64))
+
     def epilogue_info(self):
         """Launch counters of the kernels behind the sweep since the engine was made (include/lsx_hip_epilogue.h; HIP library only):
         -> dict(rows={(lanes per depth row, threads, segmented): launches of the row-mapped fast-continuum epilogue, launched ones only},
         cols=[launches per column-mapped tile list], prepass=(whole column, segmented), finish=dict(small=, levels=, lds=), finish_nt=)."""
-        if not getattr(self.lib, 'has_epilogue_info', False):
-            raise NotImplementedError('%s (%s) does not export lsx_hip_epilogue_info' % (self.lib.path, self.lib.backend))
+        self._need('epilogue_info', 'lsx_hip_epilogue_info')
         out = (C.c_int64 * 64)()
         n = self.lib.dll.lsx_hip_epilogue_info(self._h, out)
         assert n == 49, n
@@ -544,11 +575,8 @@ class Engine:
         one final-pass formal solution of the up-going rays with direction cosines `mus` (each in (0, 1], any number of them)
         for columns [col0, col0 + ncol), from the current populations and J.  Read-only.  -> [ncol][Nspect][nmu].
         Only the HIP library computes it; there is no host version."""
-        if not getattr(self.lib, 'has_emergent_rays', False):
-            raise NotImplementedError('%s (%s) does not export lsx_hip_emergent_rays: emergent spectra at arbitrary angles are '
-                                      'computed by the HIP library only' % (self.lib.path, self.lib.backend))
-        mu = f64(np.atleast_1d(np.asarray(mus, dtype=np.float64)).reshape(-1))
-        ncol = self.ncol - int(col0) if ncol is None else int(ncol)
+        self._need('emergent_rays', 'lsx_hip_emergent_rays')
+        mu, ncol = _vector(mus), self._columns(col0, ncol)
         out = np.empty((max(ncol, 0), self.problem.Nspect, mu.shape[0]), dtype=np.float64)
         self.lib.check(self.lib.dll.lsx_hip_emergent_rays(self._h, mu.shape[0], _ptr(mu), int(col0), ncol, _ptr(out), out.nbytes))
         return out
@@ -563,21 +591,15 @@ class Engine:
         approximation between them).  J is interpolated likewise, always.
         work_cap_bytes: the cap of the pass's device memory from this call on (None: unchanged; 0: the default).
         Read-only.  -> [ncol][nla][nmu].  Only the HIP library computes it; there is no host version."""
-        if not getattr(self.lib, 'has_spectrum', False):
-            raise NotImplementedError('%s (%s) does not export lsx_hip_spectrum: emergent spectra at arbitrary wavelengths are '
-                                      'computed by the HIP library only' % (self.lib.path, self.lib.backend))
-        if work_cap_bytes is not None:
-            self.lib.check(self.lib.dll.lsx_hip_spectrum_work_cap(self._h, int(work_cap_bytes)))
-        mu = f64(np.atleast_1d(np.asarray(mus, dtype=np.float64)).reshape(-1))
-        w = f64(np.atleast_1d(np.asarray(wavelength, dtype=np.float64)).reshape(-1))
+        self._need('spectrum', 'lsx_hip_spectrum')
+        self._work_cap('lsx_hip_spectrum_work_cap', work_cap_bytes)
+        mu, w, ncol = _vector(mus), _vector(wavelength), self._columns(col0, ncol)
         nla = w.shape[0]
-        ncol = self.ncol - int(col0) if ncol is None else int(ncol)
         Ncont = self.problem.Ntrans - self.problem.Nlines
         al = None if alpha is None else f64(alpha, (Ncont, nla))
         bg = [None if a is None else f64(a, (max(ncol, 0), nla, self.problem.Nspace)) for a in (bg_chi, bg_eta, bg_sca)]
         out = np.empty((max(ncol, 0), nla, mu.shape[0]), dtype=np.float64)
-        opt = lambda a: None if a is None else _ptr(a)
-        self.lib.check(self.lib.dll.lsx_hip_spectrum(self._h, nla, _ptr(w), opt(al), opt(bg[0]), opt(bg[1]), opt(bg[2]), mu.shape[0],
+        self.lib.check(self.lib.dll.lsx_hip_spectrum(self._h, nla, _ptr(w), _opt(al), _opt(bg[0]), _opt(bg[1]), _opt(bg[2]), mu.shape[0],
                                                      _ptr(mu), int(col0), ncol, _ptr(out), out.nbytes))
         return out
 
@@ -588,12 +610,9 @@ class Engine:
         .Rji_ref (the reference's rh_method.py:692 for one call), each [ncol][Ntrans][Nspace], transitions in table order.
         work_cap_bytes: the cap of the pass's device work memory from this call on (None: unchanged; 0: the default).
         Only the HIP library computes it; there is no host version."""
-        if not getattr(self.lib, 'has_radiative_rates', False):
-            raise NotImplementedError('%s (%s) does not export lsx_hip_radiative_rates: radiative rates are computed by the HIP '
-                                      'library only' % (self.lib.path, self.lib.backend))
-        if work_cap_bytes is not None:
-            self.lib.check(self.lib.dll.lsx_hip_radiative_rates_work_cap(self._h, int(work_cap_bytes)))
-        ncol = self.ncol - int(col0) if ncol is None else int(ncol)
+        self._need('radiative_rates', 'lsx_hip_radiative_rates')
+        self._work_cap('lsx_hip_radiative_rates_work_cap', work_cap_bytes)
+        ncol = self._columns(col0, ncol)
         shape = (max(ncol, 0), self.problem.Ntrans, self.problem.Nspace)
         Rij, Rji, Rji_ref = (np.empty(shape, dtype=np.float64) for _ in range(3))
         self.lib.check(self.lib.dll.lsx_hip_radiative_rates(self._h, int(col0), ncol, _ptr(Rij), _ptr(Rji), _ptr(Rji_ref), Rij.nbytes))
@@ -602,8 +621,7 @@ class Engine:
     def frequency_weights(self):
         """the weights radiative_losses uses by default: the trapezoid rule in frequency over the merged grid, [Nspect] in Hz
         (lsx_hip_frequency_weights, formed in the library's grid code)"""
-        if not getattr(self.lib, 'has_radiative_losses', False):
-            raise NotImplementedError('%s (%s) does not export lsx_hip_frequency_weights' % (self.lib.path, self.lib.backend))
+        self._need('radiative_losses', 'lsx_hip_frequency_weights')
         lam = f64(self.problem.wavelength)
         w = np.empty_like(lam)
         self.lib.check(self.lib.dll.lsx_hip_frequency_weights(lam.shape[0], _ptr(lam), _ptr(w)))
@@ -617,17 +635,13 @@ class Engine:
         wnu: [Nspect] frequency weights in Hz for F and Q (None: the trapezoid rule over the merged grid); zeros outside a band give
         the band's share.  work_cap_bytes: the cap of the pass's device work memory from this call on (None: unchanged; 0: the
         default).  Read-only.  Only the HIP library computes it; there is no host version."""
-        if not getattr(self.lib, 'has_radiative_losses', False):
-            raise NotImplementedError('%s (%s) does not export lsx_hip_radiative_losses: radiative losses are computed by the HIP '
-                                      'library only' % (self.lib.path, self.lib.backend))
+        self._need('radiative_losses', 'lsx_hip_radiative_losses')
         what = (what,) if isinstance(what, str) else tuple(what)
         unknown = [w for w in what if w not in RadiativeLosses.FIELDS]
         if unknown:
             raise ValueError('radiative_losses: unknown array(s) %s; there are %s' % (unknown, ', '.join(RadiativeLosses.FIELDS)))
-        if work_cap_bytes is not None:
-            self.lib.check(self.lib.dll.lsx_hip_radiative_losses_work_cap(self._h, int(work_cap_bytes)))
-        p = self.problem
-        ncol = self.ncol - int(col0) if ncol is None else int(ncol)
+        self._work_cap('lsx_hip_radiative_losses_work_cap', work_cap_bytes)
+        p, ncol = self.problem, self._columns(col0, ncol)
         nc = max(ncol, 0)
         shapes = {'F': (nc, p.Nspace), 'Q': (nc, p.Nspace), 'Qt': (nc, p.Ntrans, p.Nspace), 'H': (nc, p.Nspect, p.Nspace),
                   'D': (nc, p.Nspect, p.Nspace)}
@@ -646,18 +660,13 @@ class Engine:
         current populations and J.  Read-only.  what: the arrays wanted, of 'chi', 'S', 'tau', 'I', 'contrib', 'z_tau1'.
         work_cap_bytes: the cap of the pass's device memory from this call on (None: unchanged; 0: the default).
         -> DepthRays.  Only the HIP library computes it; there is no host version."""
-        if not getattr(self.lib, 'has_depth_rays', False):
-            raise NotImplementedError('%s (%s) does not export lsx_hip_depth_rays: the depth-resolved final pass is computed by the '
-                                      'HIP library only' % (self.lib.path, self.lib.backend))
+        self._need('depth_rays', 'lsx_hip_depth_rays')
         what = (what,) if isinstance(what, str) else tuple(what)
         unknown = [w for w in what if w not in DepthRays.FIELDS]
         if unknown:
             raise ValueError('depth_rays: unknown array(s) %s; there are %s' % (unknown, ', '.join(DepthRays.FIELDS)))
-        if work_cap_bytes is not None:
-            self.lib.check(self.lib.dll.lsx_hip_depth_rays_work_cap(self._h, int(work_cap_bytes)))
-        mu = f64(np.atleast_1d(np.asarray(mus, dtype=np.float64)).reshape(-1))
-        ncol = self.ncol - int(col0) if ncol is None else int(ncol)
-        nla = self.problem.Nspect - int(la0) if nla is None else int(nla)
+        self._work_cap('lsx_hip_depth_rays_work_cap', work_cap_bytes)
+        mu, ncol, nla = _vector(mus), self._columns(col0, ncol), self._window(la0, nla)
         shape = (max(ncol, 0), mu.shape[0], self.problem.Nspace, max(nla, 0))
         out = {w: np.empty(shape[:2] + shape[3:] if w == 'z_tau1' else shape, dtype=np.float64) for w in what}
         ptr = [_ptr(out[w]) if w in out else None for w in DepthRays.FIELDS]
@@ -665,10 +674,17 @@ class Engine:
                                                        int(np.prod(shape)) * 8, int(np.prod(shape[:2] + shape[3:])) * 8))
         return DepthRays(mu, la0, **out)
 
-    def _velocity_lib(self, entry):
-        if not getattr(self.lib, 'has_stokes_velocity', False):
-            raise NotImplementedError('%s (%s) does not export %s: a line-of-sight velocity per call is taken by the HIP library '
-                                      'only' % (self.lib.path, self.lib.backend, entry))
+    def _stokes_prefix(self, mus, B, gammaB, chiB, patterns, la0, nla, col0, ncol):
+        """what the entries of stokes_rays and stokes_response begin with: handle, angles, columns, window, the three fields, the four
+        pattern arrays -> (those 14 arguments, what must outlive the call, mu, the columns and the wavelengths of the outputs)"""
+        from . import zeeman
+        mu, ncol, nla = _vector(mus), self._columns(col0, ncol), self._window(la0, nla)
+        nc = max(ncol, 0)
+        fld = [self._per_depth(a, nc) for a in (B, gammaB, chiB)]
+        ncomp, alpha, strength, shift = zeeman.pack(patterns, self.problem.Nlines)
+        args = (self._h, mu.shape[0], _ptr(mu), int(col0), ncol, int(la0), nla, _ptr(fld[0]), _ptr(fld[1]), _ptr(fld[2]), _iptr(ncomp),
+                _iptr(alpha), _ptr(strength), _ptr(shift))
+        return args, (mu, fld, ncomp, alpha, strength, shift), mu, nc, max(nla, 0)
 
     def stokes_rays(self, mus, B, gammaB, chiB, patterns=None, la0=0, nla=None, col0=0, ncol=None, work_cap_bytes=None, vlos=None):
         """Emergent Stokes spectra in a magnetic field (Zeeman effect, field-free method: include/lsx_hip_stokes.h,
@@ -680,27 +696,16 @@ class Engine:
         call on (None: unchanged; 0: the default).  vlos [m/s], shaped like B: the line-of-sight velocity of this call in the place of
         the context's (include/lsx_hip_stokes_velocity.h, lsx_hip_velocity_stokes_rays; populations and J do not follow it); None: the
         context's own.  Read-only.  -> StokesRays.  Only the HIP library computes it."""
-        from . import zeeman
-        if not getattr(self.lib, 'has_stokes', False):
-            raise NotImplementedError('%s (%s) does not export lsx_hip_stokes_rays: polarised spectra are computed by the HIP '
-                                      'library only' % (self.lib.path, self.lib.backend))
-        if work_cap_bytes is not None:
-            self.lib.check(self.lib.dll.lsx_hip_stokes_rays_work_cap(self._h, int(work_cap_bytes)))
-        mu = f64(np.atleast_1d(np.asarray(mus, dtype=np.float64)).reshape(-1))
-        ncol = self.ncol - int(col0) if ncol is None else int(ncol)
-        nla = self.problem.Nspect - int(la0) if nla is None else int(nla)
-        nc, Ns = max(ncol, 0), self.problem.Nspace
-        fld = [f64(np.broadcast_to(np.asarray(a, dtype=np.float64), (nc, Ns))) for a in (B, gammaB, chiB)]
-        ncomp, alpha, strength, shift = zeeman.pack(patterns, self.problem.Nlines)
-        out = np.empty((nc, 4, max(nla, 0), mu.shape[0]), dtype=np.float64)
-        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-        args = (self._h, mu.shape[0], _ptr(mu), int(col0), ncol, int(la0), nla, _ptr(fld[0]), _ptr(fld[1]), _ptr(fld[2]), ip(ncomp),
-                ip(alpha), _ptr(strength), _ptr(shift), _ptr(out), out.nbytes)
+        self._need('stokes', 'lsx_hip_stokes_rays')
+        self._work_cap('lsx_hip_stokes_rays_work_cap', work_cap_bytes)
+        args, _keep, mu, nc, nla = self._stokes_prefix(mus, B, gammaB, chiB, patterns, la0, nla, col0, ncol)
+        out = np.empty((nc, 4, nla, mu.shape[0]), dtype=np.float64)
+        args += (_ptr(out), out.nbytes)
         if vlos is None:
             self.lib.check(self.lib.dll.lsx_hip_stokes_rays(*args))
         else:
-            self._velocity_lib('lsx_hip_velocity_stokes_rays')
-            vl = f64(np.broadcast_to(np.asarray(vlos, dtype=np.float64), (nc, Ns)))
+            self._need('stokes_velocity', 'lsx_hip_velocity_stokes_rays')
+            vl = self._per_depth(vlos, nc)
             self.lib.check(self.lib.dll.lsx_hip_velocity_stokes_rays(*args, _ptr(vl)))
         return StokesRays(mu, la0, out[:, 0], out[:, 1], out[:, 2], out[:, 3])
 
@@ -715,12 +720,8 @@ class Engine:
         the parameters (include/lsx_hip_stokes_velocity.h, lsx_hip_velocity_response_stokes; amplitude 100 m/s unless given) -- where
         'vlos' is requested and no velocity is given, the velocity is zero.  Read-only.  -> StokesResponse.  Only the HIP library
         computes it."""
-        from . import zeeman
-        if not getattr(self.lib, 'has_stokes_response', False):
-            raise NotImplementedError('%s (%s) does not export lsx_hip_response_stokes: polarised spectra and their response '
-                                      'functions are computed by the HIP library only' % (self.lib.path, self.lib.backend))
-        if work_cap_bytes is not None:
-            self.lib.check(self.lib.dll.lsx_hip_response_stokes_work_cap(self._h, int(work_cap_bytes)))
+        self._need('stokes_response', 'lsx_hip_response_stokes')
+        self._work_cap('lsx_hip_response_stokes_work_cap', work_cap_bytes)
         names = [parameters] if isinstance(parameters, str) else list(parameters)
         vel = vlos is not None or 'vlos' in names
         known = StokesResponse.VELOCITY_PARAMETERS if vel else StokesResponse.PARAMETERS
@@ -728,44 +729,31 @@ class Engine:
             if w not in StokesResponse.VELOCITY_PARAMETERS:
                 raise ValueError("stokes_response: parameter %r is not one of 'B', 'gammaB', 'chiB', 'vlos'" % (w,))
         names = [w for w in known if w in names]
-        amps = dict(StokesResponse.VELOCITY_DEFAULT_AMPLITUDES if vel else StokesResponse.DEFAULT_AMPLITUDES)
-        amps.update(amplitudes or {})
-        amp = f64(np.array([amps[w] for w in known], dtype=np.float64))
+        amps, amp = self._amplitudes(len(known), amplitudes)
         bits = sum(1 << known.index(w) for w in names)
-        mu = f64(np.atleast_1d(np.asarray(mus, dtype=np.float64)).reshape(-1))
-        ncol = self.ncol - int(col0) if ncol is None else int(ncol)
-        nla = self.problem.Nspect - int(la0) if nla is None else int(nla)
-        nc, Ns = max(ncol, 0), self.problem.Nspace
-        fld = [f64(np.broadcast_to(np.asarray(a, dtype=np.float64), (nc, Ns))) for a in (B, gammaB, chiB)]
-        ncomp, alpha, strength, shift = zeeman.pack(patterns, self.problem.Nlines)
+        args, _keep, mu, nc, nla = self._stokes_prefix(mus, B, gammaB, chiB, patterns, la0, nla, col0, ncol)
+        Ns = self.problem.Nspace
         kk = None if ks is None else np.ascontiguousarray(np.asarray(ks).reshape(-1), dtype=np.int32)
         nk = Ns if kk is None else kk.shape[0]
-        rf = np.empty((nc, len(names), 4, max(nla, 0), nk, mu.shape[0]), dtype=np.float64)
-        out = np.empty((nc, 4, max(nla, 0), mu.shape[0]), dtype=np.float64)
-        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-        args = (self._h, mu.shape[0], _ptr(mu), int(col0), ncol, int(la0), nla, _ptr(fld[0]), _ptr(fld[1]), _ptr(fld[2]), ip(ncomp),
-                ip(alpha), _ptr(strength), _ptr(shift), bits, _ptr(amp), nk, None if kk is None else ip(kk), _ptr(rf), rf.nbytes, _ptr(out),
-                out.nbytes)
+        rf = np.empty((nc, len(names), 4, nla, nk, mu.shape[0]), dtype=np.float64)
+        out = np.empty((nc, 4, nla, mu.shape[0]), dtype=np.float64)
+        args += (bits, _ptr(amp), nk, None if kk is None else _iptr(kk), _ptr(rf), rf.nbytes, _ptr(out), out.nbytes)
         if not vel:
             self.lib.check(self.lib.dll.lsx_hip_response_stokes(*args))
         else:
-            self._velocity_lib('lsx_hip_velocity_response_stokes')
-            vl = f64(np.broadcast_to(np.asarray(0.0 if vlos is None else vlos, dtype=np.float64), (nc, Ns)))
+            self._need('stokes_velocity', 'lsx_hip_velocity_response_stokes')
+            vl = self._per_depth(0.0 if vlos is None else vlos, nc)
             self.lib.check(self.lib.dll.lsx_hip_velocity_response_stokes(*args, _ptr(vl)))
         return StokesResponse({w: rf[:, i] for i, w in enumerate(names)}, StokesRays(mu, la0, out[:, 0], out[:, 1], out[:, 2], out[:, 3]),
                               np.arange(Ns, dtype=np.int32) if kk is None else kk, mu, la0, {w: float(amps[w]) for w in names})
 
     def _instrument(self, who, instrument, nla):
         """-> (the C struct of a fit.Instrument, what must outlive the call)"""
-        from . import _capi
-        if not getattr(self.lib, 'has_fit_instrument', False):
-            raise NotImplementedError('%s (%s) does not export lsx_hip_instrument_fit_normal: %s through an instrument is computed by '
-                                      'the HIP library only' % (self.lib.path, self.lib.backend, who))
+        self._need('fit_instrument', 'lsx_hip_instrument_fit_normal')
         if instrument.nla != nla:
             raise ValueError('%s: the instrument is made for %d wavelengths, the window has %d' % (who, instrument.nla, nla))
         first, weight = instrument.first, instrument.weight
-        st = _capi.LsxFitInstrument(instrument.nobs, instrument.width, first.ctypes.data_as(C.POINTER(C.c_int32)), _ptr(weight))
-        return st, (first, weight)
+        return _capi.LsxFitInstrument(instrument.nobs, instrument.width, _iptr(first), _ptr(weight)), (first, weight)
 
     def apply_instrument(self, x, instrument):
         """The instrument applied on the device, by the kernel the fit runs (include/lsx_hip_fit_instrument.h,
@@ -782,23 +770,20 @@ class Engine:
         del keep
         return out
 
-    def _fit_args(self, who, mus, basis, nnode, nodes, obs, weight, base, patterns, la0, nla, col0, ncol, work_cap_bytes, instrument=None):
+    def _fit_args(self, kind, mus, basis, nnode, nodes, obs, weight, base, patterns, la0, nla, col0, ncol, work_cap_bytes, instrument=None):
+        """what fit_field_normal and fit_field_chi2 (kind 'normal' / 'chi2') share: the checks and the 15 arguments their entries begin with"""
         from . import zeeman
-        if not getattr(self.lib, 'has_fit_field', False):
-            raise NotImplementedError('%s (%s) does not export lsx_hip_%s: the field fit is computed by the HIP library only'
-                                      % (self.lib.path, self.lib.backend, who))
-        if work_cap_bytes is not None:
-            self.lib.check(self.lib.dll.lsx_hip_fit_field_work_cap(self._h, int(work_cap_bytes)))
-        mu = f64(np.atleast_1d(np.asarray(mus, dtype=np.float64)).reshape(-1))
-        ncol = self.ncol - int(col0) if ncol is None else int(ncol)
-        nla = self.problem.Nspect - int(la0) if nla is None else int(nla)
+        who = 'fit_field_' + kind
+        self._need('fit_field', 'lsx_hip_fit_field_' + kind)
+        self._work_cap('lsx_hip_fit_field_work_cap', work_cap_bytes)
+        mu, ncol, nla = _vector(mus), self._columns(col0, ncol), self._window(la0, nla)
         nc, Ns = max(ncol, 0), self.problem.Nspace
         nn = np.ascontiguousarray(np.asarray(nnode).reshape(-1), dtype=np.int32)
         if nn.shape[0] not in (3, 4):
             raise ValueError('%s: nnode must hold three counts (B, gammaB, chiB) or four (then vlos)' % who)
         nq = nn.shape[0]
         if nq == 4:
-            self._velocity_lib('lsx_hip_velocity_%s' % who.replace('fit_field', 'fit'))
+            self._need('stokes_velocity', 'lsx_hip_velocity_fit_' + kind)
         P = max(int(nn.clip(min=0).sum()), 1)
         bas = f64(np.asarray(basis, dtype=np.float64).reshape(-1, Ns))
         if bas.shape[0] != int(nn.sum()):
@@ -809,11 +794,21 @@ class Engine:
         wt = None if weight is None else f64(np.broadcast_to(np.asarray(weight, dtype=np.float64), shape))
         bs = None if base is None else f64(np.broadcast_to(np.asarray(base, dtype=np.float64), (nc, nq, Ns)))
         ncomp, alpha, strength, shift = zeeman.pack(patterns, self.problem.Nlines)
-        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
         keep = (mu, nn, bas, x, ob, wt, bs, ncomp, alpha, strength, shift)
-        head = [self._h, mu.shape[0], _ptr(mu), int(col0), ncol, int(la0), nla, ip(ncomp), ip(alpha), _ptr(strength), _ptr(shift), ip(nn),
-                _ptr(bas), None if bs is None else _ptr(bs), _ptr(x)]
-        return head, keep, _ptr(ob), None if wt is None else _ptr(wt), nc, P, Ns, nq
+        head = [self._h, mu.shape[0], _ptr(mu), int(col0), ncol, int(la0), nla, _iptr(ncomp), _iptr(alpha), _ptr(strength), _ptr(shift),
+                _iptr(nn), _ptr(bas), _opt(bs), _ptr(x)]
+        return head, keep, _ptr(ob), _opt(wt), nc, P, Ns, nq
+
+    def _fit_call(self, kind, head, tail, nq, instrument):
+        """the one place that picks the entry of a fit: lsx_hip_fit_field_<kind> for three quantities and no instrument,
+        lsx_hip_instrument_fit_<kind> with one, lsx_hip_velocity_fit_<kind> for four quantities, its last argument the instrument or NULL"""
+        if nq == 3 and instrument is None:
+            self.lib.check(getattr(self.lib.dll, 'lsx_hip_fit_field_' + kind)(*head, *tail))
+            return
+        st, keep = (None, None) if instrument is None else self._instrument('fit_field_' + kind, instrument, head[6])
+        entry = getattr(self.lib.dll, ('lsx_hip_velocity_fit_' if nq == 4 else 'lsx_hip_instrument_fit_') + kind)
+        self.lib.check(entry(*head, *tail, None if st is None else C.byref(st)))
+        del keep
 
     def fit_field_normal(self, mus, basis, nnode, nodes, obs, weight=None, base=None, patterns=None, la0=0, nla=None, col0=0, ncol=None,
                          amplitudes=None, work_cap_bytes=None, instrument=None):
@@ -829,25 +824,12 @@ class Engine:
         (100 m/s).  The velocity is then base_3 + its nodes' expansion, never the context's own.
         -> fit.FieldNormal (.chi2, .grad, .hess, .field).  Only the HIP library computes it."""
         from .fit import FieldNormal
-        head, keep, ob, wt, nc, P, Ns, nq = self._fit_args('fit_field_normal', mus, basis, nnode, nodes, obs, weight, base, patterns, la0, nla,
-                                                       col0, ncol, work_cap_bytes, instrument)
-        amps = dict(StokesResponse.VELOCITY_DEFAULT_AMPLITUDES if nq == 4 else StokesResponse.DEFAULT_AMPLITUDES)
-        amps.update(amplitudes or {})
-        amp = f64(np.array([amps[w] for w in StokesResponse.VELOCITY_PARAMETERS[:nq]], dtype=np.float64))
+        head, keep, ob, wt, nc, P, Ns, nq = self._fit_args('normal', mus, basis, nnode, nodes, obs, weight, base, patterns, la0, nla, col0, ncol,
+                                                           work_cap_bytes, instrument)
+        amp = self._amplitudes(nq, amplitudes)[1]
         chi2, grad, hess = np.empty(nc), np.empty((nc, P)), np.empty((nc, P, P))
         field = np.empty((nc, nq, Ns))
-        if nq == 4:
-            st, keep_i = (None, None) if instrument is None else self._instrument('fit_field_normal', instrument, head[6])
-            self.lib.check(self.lib.dll.lsx_hip_velocity_fit_normal(*head, _ptr(amp), ob, wt, _ptr(chi2), _ptr(grad), _ptr(hess), _ptr(field),
-                                                                    None if st is None else C.byref(st)))
-            del keep_i
-        elif instrument is None:
-            self.lib.check(self.lib.dll.lsx_hip_fit_field_normal(*head, _ptr(amp), ob, wt, _ptr(chi2), _ptr(grad), _ptr(hess), _ptr(field)))
-        else:
-            st, keep_i = self._instrument('fit_field_normal', instrument, head[6])
-            self.lib.check(self.lib.dll.lsx_hip_instrument_fit_normal(*head, _ptr(amp), ob, wt, _ptr(chi2), _ptr(grad), _ptr(hess),
-                                                                      _ptr(field), C.byref(st)))
-            del keep_i
+        self._fit_call('normal', head, (_ptr(amp), ob, wt, _ptr(chi2), _ptr(grad), _ptr(hess), _ptr(field)), nq, instrument)
         del keep
         return FieldNormal(chi2, grad, hess, field)
 
@@ -855,19 +837,10 @@ class Engine:
                        work_cap_bytes=None, instrument=None):
         """chi2 of the field expanded from `nodes` (lsx_hip_fit_field_chi2): one Stokes pass and the reduction of fit_field_normal --
         its chi2, bit for bit.  Arguments as fit_field_normal.  -> (chi2 [ncol], field [ncol][3][Nspace], or [4] with nnode of four)."""
-        head, keep, ob, wt, nc, P, Ns, nq = self._fit_args('fit_field_chi2', mus, basis, nnode, nodes, obs, weight, base, patterns, la0, nla,
-                                                           col0, ncol, work_cap_bytes, instrument)
+        head, keep, ob, wt, nc, P, Ns, nq = self._fit_args('chi2', mus, basis, nnode, nodes, obs, weight, base, patterns, la0, nla, col0, ncol,
+                                                           work_cap_bytes, instrument)
         chi2, field = np.empty(nc), np.empty((nc, nq, Ns))
-        if nq == 4:
-            st, keep_i = (None, None) if instrument is None else self._instrument('fit_field_chi2', instrument, head[6])
-            self.lib.check(self.lib.dll.lsx_hip_velocity_fit_chi2(*head, ob, wt, _ptr(chi2), _ptr(field), None if st is None else C.byref(st)))
-            del keep_i
-        elif instrument is None:
-            self.lib.check(self.lib.dll.lsx_hip_fit_field_chi2(*head, ob, wt, _ptr(chi2), _ptr(field)))
-        else:
-            st, keep_i = self._instrument('fit_field_chi2', instrument, head[6])
-            self.lib.check(self.lib.dll.lsx_hip_instrument_fit_chi2(*head, ob, wt, _ptr(chi2), _ptr(field), C.byref(st)))
-            del keep_i
+        self._fit_call('chi2', head, (ob, wt, _ptr(chi2), _ptr(field)), nq, instrument)
         del keep
         return chi2, field
 
@@ -876,9 +849,7 @@ class Engine:
         trial = clip(nodes + delta, lo, hi), predicted = 2 d.grad - d.hess d for d = trial - nodes.  hess [ncol][P][P], grad, nodes
         [ncol][P], lam [ncol] or a scalar, lo, hi [P] or None (no bound).  -> (trial [ncol][P], predicted [ncol], status [ncol]:
         1 where the system is singular or holds a NaN; then trial = nodes, predicted = 0)."""
-        if not getattr(self.lib, 'has_fit_field', False):
-            raise NotImplementedError('%s (%s) does not export lsx_hip_fit_field_step: the field fit is computed by the HIP library '
-                                      'only' % (self.lib.path, self.lib.backend))
+        self._need('fit_field', 'lsx_hip_fit_field_step')
         g = f64(np.atleast_2d(np.asarray(grad, dtype=np.float64)))
         nc, P = g.shape
         H = f64(np.asarray(hess, dtype=np.float64).reshape(nc, P, P))
@@ -888,20 +859,17 @@ class Engine:
         hi_ = f64(np.broadcast_to(np.asarray(np.inf if hi is None else hi, dtype=np.float64), (P,)))
         trial, pred, status = np.empty((nc, P)), np.empty(nc), np.empty(nc, dtype=np.int32)
         self.lib.check(self.lib.dll.lsx_hip_fit_field_step(self._h, nc, P, _ptr(H), _ptr(g), _ptr(lm), _ptr(x), _ptr(lo_), _ptr(hi_),
-                                                           _ptr(trial), _ptr(pred), status.ctypes.data_as(C.POINTER(C.c_int32))))
+                                                           _ptr(trial), _ptr(pred), _iptr(status)))
         return trial, pred, status
 
     def _penalty(self, who, penalty, ncol, P, with_target=True):
         """-> (the C struct of a fit.Penalty, what must outlive the call)"""
-        from . import _capi
-        if not getattr(self.lib, 'has_fit_regular', False):
-            raise NotImplementedError('%s (%s) does not export lsx_hip_regular_penalty: %s is computed by the HIP library only'
-                                      % (self.lib.path, self.lib.backend, who))
+        self._need('fit_regular', 'lsx_hip_regular_penalty')
         if penalty.nparam != P:
             raise ValueError('%s: the penalty is made for %d node values, the call has %d' % (who, penalty.nparam, P))
         L = f64(penalty.L)
         tg = penalty.targets(ncol) if with_target else None
-        return _capi.LsxFitPenalty(penalty.nrow, _ptr(L), None if tg is None else _ptr(tg)), (L, tg)
+        return _capi.LsxFitPenalty(penalty.nrow, _ptr(L), _opt(tg)), (L, tg)
 
     def fit_field_penalty(self, nodes, penalty, chi2, grad=None, hess=None):
         """The penalty of a regularised fit added to what fit_field_normal / fit_field_chi2 returned for `nodes` [ncol][P]
@@ -917,8 +885,7 @@ class Engine:
         g = None if grad is None else np.array(np.asarray(grad, dtype=np.float64).reshape(nc, P), dtype=np.float64)
         H = None if hess is None else np.array(np.asarray(hess, dtype=np.float64).reshape(nc, P, P), dtype=np.float64)
         pen = np.empty(nc)
-        self.lib.check(self.lib.dll.lsx_hip_regular_penalty(self._h, nc, P, C.byref(st), _ptr(x), _ptr(c), None if g is None else _ptr(g),
-                                                            None if H is None else _ptr(H), _ptr(pen)))
+        self.lib.check(self.lib.dll.lsx_hip_regular_penalty(self._h, nc, P, C.byref(st), _ptr(x), _ptr(c), _opt(g), _opt(H), _ptr(pen)))
         del keep
         return c, g, H, pen
 
@@ -942,9 +909,7 @@ class Engine:
             raise ValueError('fit_field_uncertainty: basis has %d rows, hess is %d x %d' % (bas.shape[0], P, P))
         Ns = bas.shape[1]
         if penalty is None:
-            if not getattr(self.lib, 'has_fit_regular', False):
-                raise NotImplementedError('%s (%s) does not export lsx_hip_regular_uncertainty: the uncertainties of a fit are computed '
-                                          'by the HIP library only' % (self.lib.path, self.lib.backend))
+            self._need('fit_regular', 'lsx_hip_regular_uncertainty')
             st, keep = None, None
         else:
             st, keep = self._penalty('fit_field_uncertainty', penalty, nc, P, with_target=False)
@@ -952,18 +917,11 @@ class Engine:
         ai = np.empty((nc, P, P)) if ainv else None
         cov, sigma, status = np.empty((nc, P, P)), np.empty((nc, P)), np.empty(nc, dtype=np.int32)
         fs = np.empty((nc, nn.shape[0], Ns)) if field_sigma else None
-        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
-        self.lib.check(self.lib.dll.lsx_hip_regular_uncertainty(self._h, nc, P, _ptr(H), None if st is None else C.byref(st),
-                                                                None if sc is None else _ptr(sc), nn.shape[0], ip(nn), _ptr(bas), Ns,
-                                                                None if ai is None else _ptr(ai), _ptr(cov), _ptr(sigma),
-                                                                None if fs is None else _ptr(fs), ip(status)))
+        self.lib.check(self.lib.dll.lsx_hip_regular_uncertainty(self._h, nc, P, _ptr(H), None if st is None else C.byref(st), _opt(sc),
+                                                                nn.shape[0], _iptr(nn), _ptr(bas), Ns, _opt(ai), _ptr(cov), _ptr(sigma),
+                                                                _opt(fs), _iptr(status)))
         del keep
         return FieldUncertainty(ai, cov, sigma, fs, status, nn)
-
-    def _background_lib(self, entry):
-        if not getattr(self.lib, 'has_background', False):
-            raise NotImplementedError('%s (%s) does not export %s: the equation of state and the background opacity are computed '
-                                      'by the HIP library only' % (self.lib.path, self.lib.backend, entry))
 
     def eos(self, tables, temperature, nHTot):
         """The Wittmann equation of state of the reference's Background (include/lsx_hip_background.h, lsx_hip_eos) for
@@ -972,7 +930,7 @@ class Engine:
         witt.pe_pg evaluations per point).  A point that ends at an iteration cap raises LsxError (LSX_ENOCONV).  Does not touch
         the engine's state; any ncol.  Only the HIP library computes it."""
         from .background import EosResult
-        self._background_lib('lsx_hip_eos')
+        self._need('background', 'lsx_hip_eos')
         Ns = self.problem.Nspace
         T = f64(np.asarray(temperature, dtype=np.float64).reshape(-1, Ns))
         nH = f64(nHTot).reshape(-1, Ns)
@@ -982,8 +940,7 @@ class Engine:
         pgas, pe, part = np.empty((ncol, Ns)), np.empty((ncol, Ns)), np.empty((ncol, 17, Ns))
         status = np.zeros((ncol, Ns), dtype=np.int32)
         ctab, _keep = tables.to_c()
-        rc = self.lib.dll.lsx_hip_eos(self._h, C.byref(ctab), ncol, _ptr(T), _ptr(nH), _ptr(pgas), _ptr(pe), _ptr(part),
-                                      status.ctypes.data_as(C.POINTER(C.c_int32)))
+        rc = self.lib.dll.lsx_hip_eos(self._h, C.byref(ctab), ncol, _ptr(T), _ptr(nH), _ptr(pgas), _ptr(pe), _ptr(part), _iptr(status))
         res = EosResult(pgas, pe, part, status)
         if rc == _capi.LSX_ENOCONV:
             err = _capi.LsxError(rc, self.lib.dll.lsx_last_error().decode(errors='replace'))
@@ -999,21 +956,20 @@ class Engine:
         engine as the background of columns [col0, col0 + ncol), which set_columns must have set before.
         -> (chi, eta, sca) with chi, eta [ncol][nla][Nspace] -- what emergent_spectrum takes as bg_chi / bg_eta -- and sca
         [ncol][Nspace]; None when installing with read_back=False.  Only the HIP library computes it."""
-        self._background_lib('lsx_hip_background')
+        self._need('background', 'lsx_hip_background')
         Ns = self.problem.Nspace
         T = f64(np.asarray(temperature, dtype=np.float64).reshape(-1, Ns))
         nH, el = f64(nHTot).reshape(-1, Ns), f64(ne).reshape(-1, Ns)
         if nH.shape != T.shape or el.shape != T.shape:
             raise ValueError('temperature, nHTot and ne differ in shape')
         ncol = T.shape[0]
-        w = None if wavelength is None else f64(np.atleast_1d(np.asarray(wavelength, dtype=np.float64)).reshape(-1))
+        w = None if wavelength is None else _vector(wavelength)
         nla = self.problem.Nspect if w is None else w.shape[0]
         want = read_back or not install
         chi, eta, sca = (np.empty((ncol, nla, Ns)), np.empty((ncol, nla, Ns)), np.empty((ncol, Ns))) if want else (None, None, None)
-        opt = lambda a: None if a is None else _ptr(a)
         ctab, _keep = tables.to_c()
-        self.lib.check(self.lib.dll.lsx_hip_background(self._h, C.byref(ctab), int(col0), ncol, _ptr(T), _ptr(nH), _ptr(el), nla, opt(w),
-                                                       opt(chi), opt(eta), opt(sca), 1 if install else 0))
+        self.lib.check(self.lib.dll.lsx_hip_background(self._h, C.byref(ctab), int(col0), ncol, _ptr(T), _ptr(nH), _ptr(el), nla, _opt(w),
+                                                       _opt(chi), _opt(eta), _opt(sca), 1 if install else 0))
         return (chi, eta, sca) if want else None
 
     def convert_scales(self, tables, scale, depth_scale, temperature, nHTot, ne=None, logG=2.44, col0=0, install=False, read_back=True):
@@ -1025,9 +981,7 @@ class Engine:
         -> atmosphere.Scales with .height, .cmass, .tau_ref, .chi_ref [ncol][Nspace] (chi_ref: the continuous opacity at 500 nm,
         m^-1); None when installing with read_back=False.  Only the HIP library computes it."""
         from .atmosphere import Scales, scale_code
-        if not getattr(self.lib, 'has_scales', False):
-            raise NotImplementedError('%s (%s) does not export lsx_hip_convert_scales: the depth scales are converted by the HIP '
-                                      'library only' % (self.lib.path, self.lib.backend))
+        self._need('scales', 'lsx_hip_convert_scales')
         code = scale_code(scale)
         Ns = self.problem.Nspace
         ds = f64(np.asarray(depth_scale, dtype=np.float64).reshape(-1, Ns))
@@ -1040,11 +994,9 @@ class Engine:
         ncol = ds.shape[0]
         want = read_back or not install
         out = [np.empty((ncol, Ns)) for _ in range(4)] if want else [None] * 4
-        opt = lambda a: None if a is None else _ptr(a)
         ctab, _keep = tables.to_c()
-        self.lib.check(self.lib.dll.lsx_hip_convert_scales(self._h, C.byref(ctab), code, int(col0), ncol, _ptr(ds), _ptr(T), _ptr(nH), opt(el),
-                                                           10**logG, opt(out[0]), opt(out[1]), opt(out[2]), opt(out[3]),
-                                                           1 if install else 0))
+        self.lib.check(self.lib.dll.lsx_hip_convert_scales(self._h, C.byref(ctab), code, int(col0), ncol, _ptr(ds), _ptr(T), _ptr(nH), _opt(el),
+                                                           10**logG, *map(_opt, out), 1 if install else 0))
         return Scales(*out) if want else None
 
     def eq_pops(self, atoms, abundances, temperature, ne, nHTot, want_nTotal=True):
@@ -1057,9 +1009,7 @@ class Engine:
         bits set_atmosphere(lte_pops=True) leaves in LSX_NSTAR.  Does not touch the engine's state; any ncol.  Only the HIP
         library computes it."""
         from .eqpops import EqPops, atoms_to_c
-        if not getattr(self.lib, 'has_eq_pops', False):
-            raise NotImplementedError('%s (%s) does not export lsx_hip_eq_pops: the LTE populations are computed by the HIP '
-                                      'library only' % (self.lib.path, self.lib.backend))
+        self._need('eq_pops', 'lsx_hip_eq_pops')
         Ns = self.problem.Nspace
         T = f64(np.asarray(temperature, dtype=np.float64).reshape(-1, Ns))
         el, nH = f64(ne).reshape(-1, Ns), f64(nHTot).reshape(-1, Ns)
@@ -1069,8 +1019,7 @@ class Engine:
         carr, nlev, _keep = atoms_to_c(atoms, abundances)
         nStar = np.empty((ncol, int(sum(nlev)), Ns))
         nTotal = np.empty((ncol, len(nlev), Ns)) if want_nTotal else None
-        self.lib.check(self.lib.dll.lsx_hip_eq_pops(self._h, len(nlev), carr, ncol, _ptr(T), _ptr(el), _ptr(nH), _ptr(nStar),
-                                                    None if nTotal is None else _ptr(nTotal)))
+        self.lib.check(self.lib.dll.lsx_hip_eq_pops(self._h, len(nlev), carr, ncol, _ptr(T), _ptr(el), _ptr(nH), _ptr(nStar), _opt(nTotal)))
         return EqPops(nStar, nTotal, nlev)
 
     def configure_ng(self, order=2, delay=0):
@@ -1078,9 +1027,7 @@ class Engine:
         order 1 or 2, 0 switches it off; `delay` statistical equilibria pass before the first vector is stored.  Also takes an
         NgOptions (or None: off) as `order`.  Every column's history and counters are reset.
         Only the HIP library has it; there is no host version."""
-        if not getattr(self.lib, 'has_ng', False):
-            raise NotImplementedError('%s (%s) does not export lsx_hip_ng_configure: Ng acceleration is done by the HIP library '
-                                      'only' % (self.lib.path, self.lib.backend))
+        self._need('ng', 'lsx_hip_ng_configure')
         if order is None:
             order, delay = 0, 0
         elif isinstance(order, NgOptions):
@@ -1089,15 +1036,11 @@ class Engine:
 
     def ng_state(self, col0=0, ncol=None) -> NgState:
         """the Ng state of columns [col0, col0 + ncol) (include/lsx_hip_ng.h, lsx_hip_ng_state)"""
-        if not getattr(self.lib, 'has_ng', False):
-            raise NotImplementedError('%s (%s) does not export lsx_hip_ng_state: Ng acceleration is done by the HIP library only'
-                                      % (self.lib.path, self.lib.backend))
-        ncol = self.ncol - int(col0) if ncol is None else int(ncol)
+        self._need('ng', 'lsx_hip_ng_state')
+        ncol = self._columns(col0, ncol)
         st, ap, rj = (np.zeros(max(ncol, 0), dtype=np.int32) for _ in range(3))
         coef = np.zeros((max(ncol, 0), self.problem.Natoms, 2), dtype=np.float64)
-        ip32 = C.POINTER(C.c_int32)
-        self.lib.check(self.lib.dll.lsx_hip_ng_state(self._h, int(col0), ncol, st.ctypes.data_as(ip32), ap.ctypes.data_as(ip32),
-                                                     rj.ctypes.data_as(ip32), _ptr(coef)))
+        self.lib.check(self.lib.dll.lsx_hip_ng_state(self._h, int(col0), ncol, _iptr(st), _iptr(ap), _iptr(rj), _ptr(coef)))
         return NgState(st, ap, rj, coef)
 
     # ---- radiation boundary conditions (include/lsx_hip_boundary.h) ----
@@ -1110,70 +1053,59 @@ class Engine:
         reset it; emergent_rays, depth_rays and emergent_spectrum refuse a 'given' lower boundary.  An engine on which it has
         never been called has ('thermalised', 'zero').  Only the HIP library has it; there is no host version."""
         from . import boundary as B
-        if not getattr(self.lib, 'has_boundary', False):
-            raise NotImplementedError('%s (%s) does not export lsx_hip_set_boundary: boundary conditions other than the '
-                                      "reference's are set in the HIP library only" % (self.lib.path, self.lib.backend))
+        self._need('boundary', 'lsx_hip_set_boundary')
         if isinstance(lower, B.Boundary):
             if I_lower is not None or I_upper is not None or B.kind_code(upper) != B.ZERO:
                 raise ValueError('set_boundary: a Boundary brings its own upper kind and arrays')
             lower, upper, I_lower, I_upper = lower.lower, lower.upper, lower.I_lower, lower.I_upper
         lo, up = B.kind_code(lower), B.kind_code(upper)
-        ncol = self.ncol - int(col0) if ncol is None else int(ncol)
+        ncol = self._columns(col0, ncol)
         shape = (self.problem.Nspect, self.problem.Nrays)
         a_lo = B._array(I_lower, lo, 'lower', shape, max(ncol, 0))
         a_up = B._array(I_upper, up, 'upper', shape, max(ncol, 0))
-        self.lib.check(self.lib.dll.lsx_hip_set_boundary(self._h, int(col0), ncol, lo, up, None if a_lo is None else _ptr(a_lo),
-                                                         None if a_up is None else _ptr(a_up)))
+        self.lib.check(self.lib.dll.lsx_hip_set_boundary(self._h, int(col0), ncol, lo, up, _opt(a_lo), _opt(a_up)))
 
     def boundary_state(self, col0=0, ncol=None):
         """-> int32 [ncol][2]: the (lower, upper) kinds of columns [col0, col0 + ncol) (lsx_hip_boundary_state; boundary.ZERO,
         .THERMALISED, .GIVEN)"""
-        if not getattr(self.lib, 'has_boundary', False):
-            raise NotImplementedError('%s (%s) does not export lsx_hip_boundary_state: boundary conditions other than the '
-                                      "reference's are set in the HIP library only" % (self.lib.path, self.lib.backend))
-        ncol = self.ncol - int(col0) if ncol is None else int(ncol)
+        self._need('boundary', 'lsx_hip_boundary_state')
+        ncol = self._columns(col0, ncol)
         kinds = np.zeros((max(ncol, 0), 2), dtype=np.int32)
-        self.lib.check(self.lib.dll.lsx_hip_boundary_state(self._h, int(col0), ncol, kinds.ctypes.data_as(C.POINTER(C.c_int32))))
+        self.lib.check(self.lib.dll.lsx_hip_boundary_state(self._h, int(col0), ncol, _iptr(kinds)))
         return kinds
 
     # ---- time-dependent populations (include/lsx_hip_timedep.h) ----
-    def _time_dep_lib(self, entry):
-        if not getattr(self.lib, 'has_time_dep', False):
-            raise NotImplementedError('%s (%s) does not export %s: the time-dependent step is taken by the HIP library only'
-                                      % (self.lib.path, self.lib.backend, entry))
-
     def time_dep_start(self, dt, n_prev=None, col0=0, ncol=None):
         """Begin a time step of `dt` seconds (a scalar, or one value per column) for columns [col0, col0 + ncol)
         (lsx_hip_time_dep_start).  n_prev [ncol][NLtot][Nspace]: the populations at the start of the step; None: the columns'
         current populations, copied on the device.  The populations themselves are not touched; the range's Ng history is
         discarded.  Only the HIP library has it; there is no host version."""
-        self._time_dep_lib('lsx_hip_time_dep_start')
-        ncol = self.ncol - int(col0) if ncol is None else int(ncol)
+        self._need('time_dep', 'lsx_hip_time_dep_start')
+        ncol = self._columns(col0, ncol)
         if np.ndim(dt) == 0:
             dts = np.full(max(ncol, 0), float(dt), dtype=np.float64)
         else:
             dts = f64(dt, (max(ncol, 0),))
         prev = None if n_prev is None else f64(n_prev, (max(ncol, 0),) + self._shape(_capi.LSX_N))
-        self.lib.check(self.lib.dll.lsx_hip_time_dep_start(self._h, int(col0), ncol, _ptr(dts) if dts.size else None,
-                                                           None if prev is None else _ptr(prev)))
+        self.lib.check(self.lib.dll.lsx_hip_time_dep_start(self._h, int(col0), ncol, _ptr(dts) if dts.size else None, _opt(prev)))
 
     def time_dep_update(self) -> float:
         """one implicit update of every active column's populations from the last formal solution's Gamma, in the place of
         stat_equil (lsx_hip_time_dep_update) -> max relative population change against the iterate the call started from"""
-        self._time_dep_lib('lsx_hip_time_dep_update')
+        self._need('time_dep', 'lsx_hip_time_dep_update')
         v = C.c_double()
         self.lib.check(self.lib.dll.lsx_hip_time_dep_update(self._h, C.byref(v)))
         return v.value
 
     def time_dep_update_async(self):
         """the same, enqueued: stands where stat_equil_async stands (sync, sync_begin / sync_end, fetch_populations follow as usual)"""
-        self._time_dep_lib('lsx_hip_time_dep_update_async')
+        self._need('time_dep', 'lsx_hip_time_dep_update_async')
         self.lib.check(self.lib.dll.lsx_hip_time_dep_update_async(self._h))
 
     def time_dep_state(self, col0=0, ncol=None):
         """-> (dt [ncol], n_prev [ncol][NLtot][Nspace]) of columns [col0, col0 + ncol); dt = 0: no step started"""
-        self._time_dep_lib('lsx_hip_time_dep_state')
-        ncol = self.ncol - int(col0) if ncol is None else int(ncol)
+        self._need('time_dep', 'lsx_hip_time_dep_state')
+        ncol = self._columns(col0, ncol)
         dt = np.zeros(max(ncol, 0), dtype=np.float64)
         prev = np.zeros((max(ncol, 0),) + self._shape(_capi.LSX_N), dtype=np.float64)
         self.lib.check(self.lib.dll.lsx_hip_time_dep_state(self._h, int(col0), ncol, _ptr(dt), _ptr(prev)))
